@@ -11,12 +11,23 @@ process per GPU; every rank decodes its own independent batch of the same
 shape (frames shard with no data-path collective: weak scaling); the timed
 region is bracketed by barrier + synchronize and the max over ranks is used.
 
-The default N=1 run also measures the other BASELINE configs, each as a
+A plain run does what the headline needs and no more: set-up, warm-up, the
+--steps timed steps, the line (ms_per_step = the timed region's wall clock
+over --steps; the headline kernel's roofline comes from HIP events around
+that same region).  --dump-outputs DIR then writes what the last timed step
+computed as DIR/<name>.npy (dump_outputs; the inputs are seeded, so two
+builds run with the same arguments can be compared output for output).
+
+--full adds everything else: the oracle spot checks, the CPU baselines, the
+copy / PCIe / echo-size legs, the host-side session, echo and multicast legs,
+the N > 1 C5 job legs, and at N=1 the other BASELINE configs, each as a
 bounded leg with its own object in the line ("c3", "c4", "c5": value,
 ms_per_step, roofline of its dominant kernels -- C3 both halves of the round
 trip --, CPU baseline, spot check): C3 mask+unmask round trip of 65536 ragged
 frames, C4 fan-out of one 4 KiB payload to 10000 keys, C5 the whole 1 Mi x
-16 KiB job on this GPU.  --config c3|c4|c5 makes one of them the headline.
+16 KiB job on this GPU; the run then exits non-zero when any check fails.
+The --no-* options prune a --full run.  --config c3|c4|c5 makes one of the
+other configs the headline.
 """
 import argparse
 import gc
@@ -35,7 +46,7 @@ HBM_PEAK_GBPS = 8000.0   # MI355X HBM3E spec (MI355X_MICROARCH.md, chip-level pa
 GIB = float(1 << 30)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
@@ -53,7 +64,12 @@ def parse():
     ap.add_argument("--pmc", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"))
     ap.add_argument("--dry-run", action="store_true",
                     help="the rank launch and the line's shape only (gloo, no GPU work): tests of --gpus N")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: oracle spot checks, CPU baselines, the C3/C4/C5 legs, copy and PCIe "
+                         "legs, the host-side session / echo / multicast legs, the N > 1 C5 job legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (dump_outputs)")
+    return ap.parse_args(argv)
 
 
 XGMI_LINK_GBPS = 153.0   # one xGMI link, per direction (MI355X_MICROARCH.md)
@@ -382,6 +398,25 @@ class Workload:
                 c.fanout_many(self.payload, self.src_off, self.lens, self.ops, self.keys, wire=self.wire)
         else:
             c.encode_batch(self.payload, self.desc, wire=self.wire, wire_cap=self.cap, wire_off=self.woff)
+
+    def outputs(self):
+        """What a caller of the last step() receives, as (name, device tensor,
+        kind) with kind "bytes" (uint8), "offsets" (int64) or "info" (uint8
+        holding wsg_recv_info records): dump_outputs writes them."""
+        if self.cfg == "c2":
+            out = self.batches[self.turn ^ 1][1]   # the batch the last step decoded
+            return [("out", out, "bytes"), ("info", self.info, "info")]
+        if self.cfg == "c3":
+            return [("wire", self.wire, "bytes"), ("wire_off", self.woff, "offsets"), ("out", self.out, "bytes"),
+                    ("info", self.info, "info")]
+        if self.cfg == "c4":
+            # each message's frames, without the padding that rounds a message's
+            # block up to 128 bytes (never written)
+            from cppserver_amd.layout import frame_size
+
+            used = frame_size(0x82, True, self.length) * int(self.keys.numel())
+            return [("wire", self.wire.view(self.m, -1)[:, :used].reshape(-1), "bytes")]
+        return [("wire", self.wire, "bytes"), ("wire_off", self.woff, "offsets")]
 
     def spot_check(self):
         """One step's output at sampled frames against the oracle (the CPU
@@ -1464,6 +1499,69 @@ def warm_up(w, min_steps, seconds):
     return done
 
 
+DUMP_WHOLE_BYTES = 16 << 20    # an output whose .npy stays below this is written whole
+DUMP_SAMPLE = 1 << 22          # positions sampled from a larger one
+DUMP_BLOCK = 1 << 16           # bytes per entry of a large byte output's block sums
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(w, path, rank=0):
+    """--dump-outputs: what the last step computed (Workload.outputs), as
+    DIR/<name>.npy (rank r > 0: DIR/<name>.rank<r>.npy), under 64 MB in all.
+
+    Byte outputs are float32 (every value exact), offsets and the fields of
+    the wsg_recv_info records float64.  An output too large to write whole is
+    written as <name>_sample.npy, its values at DUMP_SAMPLE positions drawn
+    once from a fixed seed (sorted; the same positions in every run of the
+    same shape), and, for bytes, <name>_block_sums.npy, the sum of every
+    DUMP_BLOCK-byte block of the whole output (float64, exact), so that every
+    byte bears on the dump.  Returns {file name: shape}."""
+    import torch
+
+    import cppserver_amd as ca
+
+    os.makedirs(path, exist_ok=True)
+    suffix = ".npy" if rank == 0 else ".rank%d.npy" % rank
+    written = {}
+
+    def save(name, arr):
+        np.save(os.path.join(path, name + suffix), arr)
+        written[name + suffix] = list(arr.shape)
+
+    def sample_of(t, dtype):
+        n = int(t.numel())
+        pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLE))
+        return t[torch.from_numpy(pos).to(t.device)].to(dtype).cpu().numpy()
+
+    for name, t, kind in w.outputs():
+        t = t.reshape(-1)
+        n = int(t.numel())
+        if kind == "info":
+            rec = ca.info_to_numpy(t, n // ca.RECV_INFO.itemsize)
+            for field in rec.dtype.names:
+                if not field.startswith("_"):
+                    save("%s_%s" % (name, field), rec[field].astype(np.float64))
+        elif kind == "offsets":
+            if n * 8 <= DUMP_WHOLE_BYTES:
+                save(name, t.cpu().numpy().astype(np.float64))
+            else:
+                save(name + "_sample", sample_of(t, torch.float64))
+        elif n * 4 <= DUMP_WHOLE_BYTES:
+            save(name, t.cpu().numpy().astype(np.float32))
+        else:
+            save(name + "_sample", sample_of(t, torch.float32))
+            whole = n // DUMP_BLOCK * DUMP_BLOCK
+            sums = []
+            step = DUMP_BLOCK << 12   # 256 MiB of the output per reduction
+            for a in range(0, whole, step):
+                b = min(a + step, whole)
+                sums.append(t[a:b].view(-1, DUMP_BLOCK).sum(dim=1, dtype=torch.int64).cpu())
+            if whole < n:
+                sums.append(t[whole:].sum(dtype=torch.int64).reshape(1).cpu())
+            save(name + "_block_sums", torch.cat(sums).numpy().astype(np.float64))
+    return written
+
+
 CHECK_KEYS = ("spot_check", "root_check", "check", "payload_ok", "delivered_ok", "roundtrip_ok", "all_delivered",
               "wire_ok", "off_ok")
 
@@ -1507,12 +1605,14 @@ def main():
     # GPU idle) comes first, so that the warm-up steps run right before the
     # timed region: the first launch after an idle GPU takes 150-165 us
     # instead of 86 (tools/ramp.py), 4 % of a 20-step region
-    ok = w.spot_check()
+    full = args.full   # without it: set up, warm up, the timed steps, the line
+    ok = w.spot_check() if full else None
     for _ in range(args.warmup):
         w.step()
     codec.sync()
 
     r = timed_region(w, args.steps, world, device)
+    dumped = dump_outputs(w, args.dump_outputs, rank) if args.dump_outputs else None
     elapsed = r["elapsed"]
     ms_per_step = elapsed / args.steps * 1e3
     value = world * w.payload_bytes * args.steps / elapsed / GIB
@@ -1532,19 +1632,19 @@ def main():
               # after the first) and the rest, first-launch latency + wake-up
               "region_host": {"submit_ms": round(r["submit_ms"], 4),
                               "wall_minus_events_ms": round(elapsed * 1e3 - r["region_event_ms"], 4)}}
-    if w.cfg == "c5" and world > 1:
+    if full and w.cfg == "c5" and world > 1:
         # the exchange step: the job's shards encoded and gathered to rank 0
         # by the product's rank form (RCCL inside the library)
         try:
             extras["c5_job"] = c5_rank_leg(world, rank, local, device)
         except Exception as e:   # noqa: BLE001
             extras["c5_job"] = {"error": repr(e)[:300]}
-    if w.cfg == "c2" and world > 1 and not args.no_extras:
+    if full and w.cfg == "c2" and world > 1 and not args.no_extras:
         try:
             extras["pcie_inclusive_all_ranks"] = pcie_all_ranks_leg(w, world, rank, device)
         except Exception as e:   # noqa: BLE001  (reported; the headline stands)
             extras["pcie_inclusive_all_ranks"] = {"error": repr(e)[:300]}
-    if w.cfg == "c2" and world > 1 and not args.no_c5_job:
+    if full and w.cfg == "c2" and world > 1 and not args.no_c5_job:
         # C5 (BASELINE configs[4]) on the same GPUs through the product's RCCL
         # rank form; a failure is reported in the line (and fails the run, see
         # failed_checks), it does not take the headline's numbers with it
@@ -1568,11 +1668,11 @@ def main():
                 extras["c5_job_torch_crosscheck"] = c5_job_leg(world, rank, device, codec, n_total=c5_frames)
             except Exception as e:   # noqa: BLE001
                 extras["c5_job_torch_crosscheck"] = {"error": repr(e)[:300]}
-    cpu = host_cpu() if (rank == 0 and world == 1 and not args.no_cpu) else None
+    cpu = host_cpu() if (full and rank == 0 and world == 1 and not args.no_cpu) else None
     headline_cpu = {}
     if cpu is not None:
         defer_cpu_baseline(headline_cpu, w, args.cpu_seconds)
-    if rank == 0 and world == 1 and not args.no_extras:
+    if full and rank == 0 and world == 1 and not args.no_extras:
         extras["torch_copy_GBps"] = round(torch_copy_rate(w), 1)   # for scale, not a ceiling (torch_copy_rate)
         pc = pcie_inclusive(w)
         if pc is not None:
@@ -1590,7 +1690,7 @@ def main():
     # the other BASELINE configs (C3 round trip, C4 fan-out, C5 1 Mi x 16 KiB
     # job on this GPU), each a bounded leg with its own roofline and CPU
     # baseline, after the headline's own region (its inputs are freed first)
-    if headline_cfg == "c2" and world == 1 and not args.no_configs:
+    if full and headline_cfg == "c2" and world == 1 and not args.no_configs:
         for cfg, steps, warm in SUB_CONFIGS:
             try:
                 extras[cfg] = config_obj(args, cfg, codec, rank, world, device, steps, warm, cpu)
@@ -1602,7 +1702,7 @@ def main():
     # profiler follows child processes, and tracing their ~1e5 small launches
     # per second takes minutes; the GPU legs above are unchanged by it)
     host_legs = os.environ.get("WSG_BENCH_HOST_LEGS", "1") != "0"
-    if rank == 0 and world == 1 and not args.no_extras and headline_cfg == "c2" and host_legs:
+    if full and rank == 0 and world == 1 and not args.no_extras and headline_cfg == "c2" and host_legs:
         # the legs' processes on the GPU's NUMA node (inherited affinity;
         # the reference-algorithm legs alike), this thread's mask restored after
         node, cpus = gpu_node_cpus(local)
@@ -1629,7 +1729,7 @@ def main():
         run_deferred_cpu_baselines(cpu)
     cpu1, cpu_mt = headline_cpu.get("cpu_baseline"), headline_cpu.get("cpu_baseline_mt")
 
-    if world > 1:
+    if full and world > 1:
         import torch.distributed as dist
 
         okt = torch.tensor([1 if ok else 0])
@@ -1657,17 +1757,20 @@ def main():
             "roofline": roof,
             "cpu_baseline": cpu1,
             "cpu_baseline_mt": cpu_mt,
-            "spot_check": ok,
+            "full": full,
         }
         line.update(extras)
-        failed = failed_checks(extras)
-        if not ok:
-            failed.insert(0, "spot_check (headline)")
-        # the top-level spot_check is every leg's parity check and root check
-        # together; the headline's own stays beside it
-        line["spot_check_headline"] = ok
-        line["spot_check"] = not failed
-        line["failed_checks"] = failed
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
+        if full:
+            failed = failed_checks(extras)
+            if not ok:
+                failed.insert(0, "spot_check (headline)")
+            # the top-level spot_check is every leg's parity check and root check
+            # together; the headline's own stays beside it
+            line["spot_check_headline"] = ok
+            line["spot_check"] = not failed
+            line["failed_checks"] = failed
         print(json.dumps(line), flush=True)
         if failed:
             print("bench.py: %d failed check(s) or leg error(s): %s" % (len(failed), "; ".join(failed)),

@@ -42,6 +42,16 @@ def test_failed_checks_finds_misses_and_errors():
     assert len(got) == 6
 
 
+def test_full_and_dump_outputs_are_off_by_default():
+    """A plain run is the headline alone: --full and --dump-outputs are
+    options, off unless given."""
+    b = _bench()
+    a = b.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = b.parse(["--full", "--dump-outputs", "some/dir"])
+    assert a.full is True and a.dump_outputs == "some/dir"
+
+
 def test_bench_gpus_n_starts_n_ranks():
     """`python bench.py --gpus 2` (the driver's N=1 command shape with N=2)
     starts two ranks itself (torch.distributed.run as a child process) and the

@@ -414,7 +414,7 @@ def test_bench_n2_c5_rank_form():
                WSG_BENCH_HOST_LEGS="0", NCCL_DEBUG="VERSION")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29533", os.path.join(root, "bench.py"),
-                        "--gpus", "2", "--steps", "5", "--warmup", "2", "--no-extras"],
+                        "--gpus", "2", "--steps", "5", "--warmup", "2", "--full", "--no-extras"],
                        capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])

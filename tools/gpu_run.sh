@@ -24,9 +24,9 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
     if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
     step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $?
 fi
-step bench 600 python bench.py --steps ${STEPS:-20} --warmup 3 ${BENCH_ARGS:-} || exit $?
+step bench 600 python bench.py --full --steps ${STEPS:-20} --warmup 3 ${BENCH_ARGS:-} || exit $?
 if [ "${SKIP_PROF:-0}" != "1" ]; then
     step rocprof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
-        python bench.py --steps ${STEPS:-20} --warmup 3 --no-cpu --no-extras ${BENCH_ARGS:-} || exit $?
+        python bench.py --full --steps ${STEPS:-20} --warmup 3 --no-cpu --no-extras ${BENCH_ARGS:-} || exit $?
 fi
 echo "== done"

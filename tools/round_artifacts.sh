@@ -1,6 +1,6 @@
 #!/bin/bash
 # One round's evidence for profiles/$ROUND (ROUND=r4 ...), in one GPU call:
-#  * the driver's own command (python bench.py --steps 20 --warmup 5): the
+#  * the whole bench line (python bench.py --full --steps 20 --warmup 5): the
 #    C2 headline line with its c3 / c4 / c5 objects;
 #  * the same command under rocprofv3 --kernel-trace --marker-trace --stats
 #    (bench.py marks every leg's timed region with a roctx range, so
@@ -25,12 +25,12 @@ run() {   # name, timeout, command...
     timeout -k 10 "$t" "$@" > "$OUT/$name.out" 2> "$OUT/$name.err" || { echo "FAILED $name rc=$?" | tee -a "$OUT/progress.log"; exit 1; }
 }
 if [ "${BENCH:-1}" = 1 ]; then
-    run bench 600 python bench.py --steps 20 --warmup 5
+    run bench 600 python bench.py --full --steps 20 --warmup 5
     # the same command; its host-side child legs (echo, multicast, session
     # batches: no kernel of the GPU legs) are skipped, tracing them takes minutes
     export WSG_BENCH_HOST_LEGS=0
     run trace 900 rocprofv3 --kernel-trace --marker-trace --stats -d "$OUT/trace" -o run \
-        --output-format csv -- python bench.py --steps 20 --warmup 5
+        --output-format csv -- python bench.py --full --steps 20 --warmup 5
     unset WSG_BENCH_HOST_LEGS
 fi
 [ "${PMC:-1}" = 1 ] && for c in ${CFGS:-c2 c3 c4 c5}; do
