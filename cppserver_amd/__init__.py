@@ -14,8 +14,9 @@ import os
 import numpy as np
 
 from .layout import (  # noqa: F401  (re-exported)
-    CB_CLOSE, CB_PING, CB_PONG, CB_RECEIVED, RECV_INFO, SEND_DESC, WS_BINARY, WS_CLOSE, WS_FIN, WS_PING,
-    WS_PONG, WS_TEXT, WSG_EHIP, WSG_EINVAL, WSG_ENOMEM, WSG_ETRUNC, WSG_OK, frame_size, frame_sizes, key_from_bytes,
+    CB_CLOSE, CB_PING, CB_PONG, CB_RECEIVED, MSG, RECV_INFO, SEND_DESC, STREAM_STATE, WS_BINARY, WS_CLOSE, WS_FIN,
+    WS_PING, WS_PONG, WS_TEXT, WSG_EHIP, WSG_EINVAL, WSG_ENOMEM, WSG_ETRUNC, WSG_OK, frame_size, frame_sizes,
+    key_from_bytes, message_plan,
 )
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -60,6 +61,7 @@ def lib(path=None):
         "wsg_sync": (ci, [vp, vp]),
         "wsg_stream": (vp, [vp]),
         "wsg_decode_batch": (ci, [vp, vp, u64, vp, u32, vp, vp, vp]),
+        "wsg_decode_messages": (ci, [vp, vp, u64, vp, u32, vp, u32, vp, vp, u64, vp, vp, vp, vp]),
         "wsg_encode_batch": (ci, [vp, vp, vp, u32, vp, u64, vp, vp]),
         "wsg_fanout_encode": (ci, [vp, vp, u64, vp, u32, ctypes.c_uint8, ci, vp, u64, vp]),
         "wsg_fanout_encode_many": (ci, [vp, vp, vp, vp, vp, u32, vp, u32, ci, vp, u64, vp, vp]),
@@ -229,6 +231,49 @@ class Codec:
                                       self._stream(stream))
         _check(rc, "wsg_decode_batch")
         return out, info
+
+    # -- batch decode to messages (unmask + assemble + pack) -----------------
+    def decode_messages(self, wire, frame_start, stream_first, state=None, msg=None, msg_cap=None, stream=None,
+                        msgs=None, count=None, info=None):
+        """wsg_decode_messages: the frames of ``wire`` (as decode_batch),
+        grouped into streams by ``stream_first`` (int32 CUDA tensor of
+        n_streams + 1 frame indices), assembled into messages and packed
+        densely.  ``state``: uint8 CUDA tensor of n_streams * 8 bytes
+        (STREAM_STATE; None: zeros), updated in place.  Returns (msg, msgs,
+        count, state, info): the message bytes, the MSG table bytes (room for n
+        records, count[0] valid), count int64[2] = [messages, bytes used], the
+        new state and the RECV_INFO bytes.  ``msg_cap`` defaults to the wire's
+        length, which always suffices."""
+        t = self._torch
+        n = int(frame_start.numel())
+        ns = int(stream_first.numel()) - 1
+        if ns < 0 or stream_first.element_size() != 4:
+            raise WSGError(WSG_EINVAL, "decode_messages: stream_first must hold n_streams + 1 32-bit indices")
+        dev = wire.device
+        if state is None:
+            state = t.zeros(max(ns, 1) * STREAM_STATE.itemsize, dtype=t.uint8, device=dev)
+        if msg_cap is None:
+            msg_cap = int(wire.numel()) if msg is None else int(msg.numel())
+        cap = int(msg_cap)
+        if msg is None:
+            msg = t.empty(max(cap, 16), dtype=t.uint8, device=dev)
+        if msgs is None:
+            msgs = t.empty(max(n, 1) * MSG.itemsize, dtype=t.uint8, device=dev)
+        if count is None:
+            count = t.empty(2, dtype=t.int64, device=dev)
+        if info is None:
+            info = t.empty(max(n, 1) * RECV_INFO.itemsize, dtype=t.uint8, device=dev)
+        if (cap > int(msg.numel()) or int(state.numel()) < ns * STREAM_STATE.itemsize
+                or int(msgs.numel()) < n * MSG.itemsize or int(info.numel()) < n * RECV_INFO.itemsize):
+            raise WSGError(WSG_EINVAL, "decode_messages: a buffer is smaller than the batch needs")
+        rc = self._L.wsg_decode_messages(self._ctx, ctypes.c_void_p(wire.data_ptr()), wire.numel(),
+                                         ctypes.c_void_p(frame_start.data_ptr()), n,
+                                         ctypes.c_void_p(stream_first.data_ptr()), ns,
+                                         ctypes.c_void_p(state.data_ptr()), ctypes.c_void_p(msg.data_ptr()), cap,
+                                         ctypes.c_void_p(msgs.data_ptr()), ctypes.c_void_p(count.data_ptr()),
+                                         ctypes.c_void_p(info.data_ptr()), self._stream(stream))
+        _check(rc, "wsg_decode_messages")
+        return msg, msgs, count, state, info
 
     def prepare_decode(self, wire, frame_start, out, info, stream=None):
         """wsg_decode_batch on fixed buffers (a server's batch arena), with

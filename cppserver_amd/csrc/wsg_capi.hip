@@ -68,6 +68,11 @@ struct wsg_ctx {
     unsigned long long* h_err_copy = nullptr;   // page-locked: d_err_host after a large in-place decode
     // scratch
     wsg_enc_scratch enc;
+    // wsg_decode_messages: the plan block (wsg::msg_plan_layout) and the gather's piece records
+    uint8_t* d_msg_plan = nullptr;
+    uint64_t msg_plan_cap = 0;
+    wsg::MsgPiece* d_msg_pieces = nullptr;
+    uint64_t msg_pieces_cap = 0;
     // staging for host entry points
     uint8_t* d_stage = nullptr;
     uint8_t* h_stage = nullptr;
@@ -1023,6 +1028,8 @@ int wsg_destroy(wsg_ctx* c)
     if (c->h_err_copy)
         (void)hipHostFree(c->h_err_copy);
     free_enc(c->enc);
+    (void)hipFree(c->d_msg_plan);
+    (void)hipFree(c->d_msg_pieces);
     (void)hipFree(c->d_stage);
     (void)hipFree(c->d_fs);
     (void)hipFree(c->d_info);
@@ -1120,6 +1127,51 @@ int wsg_decode_batch(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const
                      !in_alloc(d_frame_start, uint64_t(n) * 8) || !in_alloc(d_info, uint64_t(n) * sizeof(wsg_recv_info))))
         return WSG_EINVAL;
     return decode_launch(c, d_wire, wire_len, d_frame_start, n, d_out, d_info, pick(c, stream), c->d_err);
+}
+
+// Messages out of a batch of frames: the plan pass (a few small kernels, one
+// lane per frame or per stream), then the gather, which moves every
+// delivered payload byte once.
+int wsg_decode_messages(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const uint64_t* d_frame_start,
+                        uint32_t n, const uint32_t* d_stream_first, uint32_t n_streams, wsg_stream_state* d_state,
+                        uint8_t* d_msg, uint64_t msg_cap, wsg_msg* d_msgs, uint64_t* d_count, wsg_recv_info* d_info,
+                        void* stream)
+{
+    if (!c || !d_count || !d_stream_first || (wire_len && !d_wire) || (msg_cap && !d_msg) ||
+        (n && (!d_frame_start || !d_info || !d_msgs || n_streams == 0)) || (n_streams && !d_state) ||
+        n == UINT32_MAX || n_streams == UINT32_MAX)
+        return WSG_EINVAL;
+    if (!aligned16(d_wire) || !aligned16(d_msg))
+        return WSG_EINVAL;
+    if (c->check &&
+        (!in_alloc(d_wire, (wire_len + 15) & ~uint64_t(15)) || !in_alloc(d_frame_start, uint64_t(n) * 8) ||
+         !in_alloc(d_stream_first, (uint64_t(n_streams) + 1) * 4) ||
+         !in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) || !in_alloc(d_msg, msg_cap) ||
+         !in_alloc(d_msgs, uint64_t(n) * sizeof(wsg_msg)) || !in_alloc(d_count, 2 * 8) ||
+         !in_alloc(d_info, uint64_t(n) * sizeof(wsg_recv_info))))
+        return WSG_EINVAL;
+    hipStream_t s = pick(c, stream);
+    // pieces: at most len / PIECE + 2 per delivered frame, and the delivered
+    // payloads of a well-formed batch are disjoint ranges of the wire (the
+    // kernels clamp to this bound whatever the batch holds)
+    const uint64_t pieces_cap = wire_len / wsg::PIECE + 2 * uint64_t(n) + 1;
+    if (pieces_cap > UINT32_MAX)
+        return WSG_EINVAL;
+    if (int rc = ensure_array(c->d_msg_plan, c->msg_plan_cap, wsg::msg_plan_layout(nullptr, n, nullptr)))
+        return rc;
+    if (int rc = ensure_array(c->d_msg_pieces, c->msg_pieces_cap, pieces_cap))
+        return rc;
+    wsg::MsgPlan plan;
+    wsg::msg_plan_layout(c->d_msg_plan, n, &plan);
+    WSG_HIP(wsg::launch_msg_plan(s, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams, d_state, msg_cap,
+                                 d_msgs, d_count, d_info, plan, c->d_msg_pieces, pieces_cap, c->d_err));
+    if (n == 0)
+        return WSG_OK;
+    const int t = timing_begin(c, s);
+    WSG_HIP(wsg::launch_msg_gather(s, grid_for(c, ceil_div(pieces_cap, wsg::BLOCK / 64), c->enc_blocks_per_cu), d_wire,
+                                   plan, c->d_msg_pieces, pieces_cap, d_msg, msg_cap));
+    timing_end(c, s, t);
+    return WSG_OK;
 }
 
 namespace {

@@ -68,6 +68,54 @@ hipError_t launch_encode_scan_small(hipStream_t s, const wsg_send_desc* desc, ui
 hipError_t launch_encode_small(hipStream_t s, const uint8_t* payload, const wsg_send_desc* desc, uint32_t n,
                                uint64_t* wire_off, const uint64_t* scan, uint8_t* wire, uint64_t wire_cap,
                                unsigned long long* err);
+// ---- message assembly (wsg_decode_messages) --------------------------------
+// Plan scratch of one call, carved by the host out of one device block
+// (msg_plan_layout): per-frame scan results, per-block partials (one block =
+// BLOCK frames), the totals.
+struct MsgPlan {
+    uint64_t* dst;        // n: offset in d_msg of each frame's payload (delivered bytes before it)
+    uint64_t* bbytes;     // nb: block sums of delivered bytes, then their exclusive prefixes
+    uint64_t* bbytes_pre;
+    uint64_t* bpc;        // nb: block sums of pieces, then their exclusive prefixes
+    uint64_t* bpc_pre;
+    uint64_t* tot;        // [0] FIN frames, [1] last FIN frame + 1, [2] delivered bytes, [3] pieces
+    // per frame, block-local: the batch-wide value is the entry combined with
+    // its block's prefix (the kernels never rewrite an entry in place, so a
+    // lane may read any frame's while others run)
+    uint32_t* finx;       // n: FIN frames before frame i
+    uint32_t* pinc;       // n: 1 + last frame <= i that heads a stream or names an opcode (0: none)
+    uint32_t* qx;         // n: 1 + last FIN frame < i (0: none)
+    uint32_t* sidx;       // n: the frame's stream
+    uint32_t* pstart;     // n: pieces before frame i
+    uint32_t* bfin;       // nb each: block partials and their exclusive prefixes
+    uint32_t* bfin_pre;
+    uint32_t* bp;
+    uint32_t* bp_pre;
+    uint32_t* bq;
+    uint32_t* bq_pre;
+};
+// Bytes of that block for n frames; plan (or null) gets the pointers into base.
+uint64_t msg_plan_layout(uint8_t* base, uint32_t n, MsgPlan* plan);
+// One work piece of the gather, everything its wave needs in one 32-byte
+// scalar load (a piece -> frame map as the encode's put three dependent
+// loads between a wave's start and its first data load).
+struct alignas(32) MsgPiece {
+    uint64_t poff;   // wire offset of the frame's payload
+    uint64_t d0;     // offset in d_msg of the payload's first byte
+    uint64_t len;    // payload bytes
+    uint32_t key;
+    uint32_t k;      // piece of the frame: [A + k * PIECE, A + (k + 1) * PIECE) of d_msg, A = d0 & ~(PIECE_ALIGN - 1)
+};
+// The plan pass: d_info, d_msgs, d_count, d_state, the plan and the piece
+// records (pieces_cap entries); latches frame errors and WSG_ENOMEM.
+hipError_t launch_msg_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
+                           const uint32_t* stream_first, uint32_t n_streams, wsg_stream_state* state, uint64_t msg_cap,
+                           wsg_msg* msgs, uint64_t* count, wsg_recv_info* info, const MsgPlan& plan,
+                           MsgPiece* pieces, uint64_t pieces_cap, unsigned long long* err);
+// The gather pass: every delivered payload byte, unmasked, to its place in msg.
+hipError_t launch_msg_gather(hipStream_t s, int grid, const uint8_t* wire, const MsgPlan& plan,
+                             const MsgPiece* pieces, uint64_t pieces_cap, uint8_t* msg, uint64_t msg_cap);
+
 // Messages of one fan-out launch (blockIdx.y): payload and output offsets.
 constexpr int FAN_MSGS = 32;
 struct FanMsgs {

@@ -1,7 +1,8 @@
 """Record layouts shared by the C-ABI (include/wsg_capi.h) and its callers.
 
-numpy structured dtypes whose byte layout is exactly ``wsg_send_desc`` and
-``wsg_recv_info``; importing this module loads no native code.
+numpy structured dtypes whose byte layout is exactly ``wsg_send_desc``,
+``wsg_recv_info``, ``wsg_msg`` and ``wsg_stream_state``; importing this module
+loads no native code.
 """
 import numpy as np
 
@@ -37,6 +38,28 @@ RECV_INFO = np.dtype(
 
 assert SEND_DESC.itemsize == 32 and RECV_INFO.itemsize == 32
 
+# wsg_msg: one assembled message of wsg_decode_messages, what the session
+# hands to its callback at a FIN frame (reference ws.cpp:411-452).
+MSG = np.dtype(
+    [
+        ("off", "<u8"),
+        ("len", "<u8"),
+        ("stream", "<u4"),
+        ("first_frame", "<u4"),
+        ("nframes", "<u4"),
+        ("status", "<i4"),
+        ("kind", "u1"),
+        ("opcode", "u1"),
+        ("_pad", "u1", (6,)),
+    ]
+)
+
+# wsg_stream_state: what a connection carries from one wsg_decode_messages
+# call to the next.
+STREAM_STATE = np.dtype([("consumed", "<u4"), ("opcode", "u1"), ("_pad", "u1", (3,))])
+
+assert MSG.itemsize == 40 and STREAM_STATE.itemsize == 8
+
 # Opcode byte values (reference include/server/ws/ws.h:33-43).
 WS_FIN, WS_TEXT, WS_BINARY, WS_CLOSE, WS_PING, WS_PONG = 0x80, 0x01, 0x02, 0x08, 0x09, 0x0A
 
@@ -69,3 +92,59 @@ def frame_sizes(desc):
     body = length + np.where(prefix, 2, 0).astype(np.uint64)
     hdr = np.where(body < 126, 2, np.where(body < 65536, 4, 10)).astype(np.uint64)
     return hdr + np.where(desc["mask"] != 0, 4, 0).astype(np.uint64) + body
+
+
+def message_plan(info, stream_first, state=None, payload=None):
+    """The plan pass of wsg_decode_messages restated on the host: which
+    frames make which messages (reference ws.cpp:399-452).
+
+    ``info``: RECV_INFO of the batch's frames; ``stream_first``: n_streams + 1
+    frame indices, stream j's frames are [stream_first[j], stream_first[j+1])
+    in arrival order; ``state``: STREAM_STATE per stream (None: zeros).
+    Returns (msgs, count, new_state): the MSG table in the order of the FIN
+    frames, count = [messages, bytes of the dense message buffer], and each
+    stream's frames consumed and _ws_opcode for the next call.
+
+    A close message's status is the first two bytes of its buffer
+    (ws.cpp:435-439), so it needs bytes: ``payload`` is the batch with its
+    payloads unmasked where they sit (wsg_decode_batch's output); without it
+    such a status is left 0.
+    """
+    info = np.asarray(info, dtype=RECV_INFO)
+    stream_first = np.asarray(stream_first, dtype=np.int64)
+    n_streams = len(stream_first) - 1
+    new_state = np.zeros(n_streams, dtype=STREAM_STATE)
+    if state is not None:
+        new_state["opcode"] = np.asarray(state, dtype=STREAM_STATE)["opcode"]
+    kinds = {WS_TEXT: CB_RECEIVED, WS_BINARY: CB_RECEIVED, WS_CLOSE: CB_CLOSE, WS_PING: CB_PING, WS_PONG: CB_PONG}
+    msgs, used = [], 0
+    for j in range(n_streams):
+        lo, hi = int(stream_first[j]), int(stream_first[j + 1])
+        fins = [i for i in range(lo, hi) if info["fin"][i]]
+        opcode = int(new_state["opcode"][j])          # _ws_opcode: sticky, never reset (ws.cpp:326)
+        first = lo                                    # the open message's first frame
+        for i in range(lo, fins[-1] + 1 if fins else lo):   # frames after the last FIN frame: the tail
+            opcode = int(info["opcode"][i]) or opcode
+            if not info["fin"][i]:
+                continue
+            frames = range(first, i + 1)              # every frame since the previous FIN, control frames too
+            size = int(sum(int(info["len"][k]) for k in frames))
+            m = np.zeros((), dtype=MSG)
+            m["off"], m["len"], m["stream"], m["first_frame"], m["nframes"] = used, size, j, first, len(frames)
+            m["kind"], m["opcode"] = kinds.get(opcode, 0), opcode
+            if opcode == WS_CLOSE:
+                m["status"] = 1000
+                if size >= 2:                         # the status leaves the callback's data
+                    m["off"], m["len"] = used + 2, size - 2
+                    m["status"] = 0
+                    if payload is not None:
+                        head = b"".join(bytes(payload[int(info["payload_off"][k]):][:int(info["len"][k])])[:2]
+                                        for k in frames)[:2]
+                        m["status"] = head[0] << 8 | head[1]
+            msgs.append(m)
+            used += size
+            first = i + 1
+        new_state["consumed"][j] = first - lo
+        new_state["opcode"][j] = opcode
+    table = np.array(msgs, dtype=MSG) if msgs else np.zeros(0, dtype=MSG)
+    return table, np.array([len(msgs), used], dtype=np.uint64), new_state

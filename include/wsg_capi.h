@@ -111,6 +111,59 @@ int wsg_decode_batch(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
                      const uint64_t* d_frame_start, uint32_t n,
                      uint8_t* d_out, wsg_recv_info* d_info, void* stream);
 
+/* ---- batch decode to messages (the second half of PrepareReceiveFrame) --- */
+/* (Added without an ABI bump: WSG_ABI_VERSION stays 3, the change only adds
+ * symbols and structs; nothing existing moved.)
+ * One assembled message: what the session would hand to onWSReceived /
+ * onWSClose / onWSPing / onWSPong at a FIN frame (ws.cpp:411-452). */
+typedef struct wsg_msg {
+    uint64_t off;          /* offset of the callback's data in d_msg (past a close status) */
+    uint64_t len;          /* the callback's size (close: without the 2 status bytes)     */
+    uint32_t stream;       /* index of the stream                                          */
+    uint32_t first_frame;  /* index in d_frame_start of the message's first frame         */
+    uint32_t nframes;      /* frames accumulated into it (>= 1)                            */
+    int32_t  status;       /* close: ws.cpp:431-439 (1000 when < 2 bytes); otherwise 0     */
+    uint8_t  kind;         /* WSG_CB_*; 0 = no callback (unknown sticky opcode, Q6)        */
+    uint8_t  opcode;       /* _ws_opcode at the FIN frame                                  */
+    uint8_t  _pad[6];      /* written as 0 */
+} wsg_msg;                 /* 40 bytes */
+
+typedef struct wsg_stream_state {
+    uint32_t consumed;     /* out: frames of this stream that went into messages          */
+    uint8_t  opcode;       /* in: _ws_opcode before the stream's first frame;
+                              out: _ws_opcode after its last consumed frame                */
+    uint8_t  _pad[3];      /* written as 0 */
+} wsg_stream_state;        /* 8 bytes */
+
+/* wsg_decode_batch's frames, assembled into messages (ws.cpp:399-452) and
+ * packed densely: the layout wsg_encode_batch takes its payloads in.
+ * d_wire / wire_len / d_frame_start / n / d_info: as wsg_decode_batch (d_info
+ * gets the same records; d_wire is only read).  d_stream_first[0..n_streams]:
+ * non-decreasing, [0] = 0, [n_streams] = n; frames [d_stream_first[j],
+ * d_stream_first[j+1]) are connection j's frames in arrival order (empty
+ * streams allowed).  Within a stream every FIN frame ends a message whose
+ * buffer is the unmasked payloads of all the stream's frames since its
+ * previous FIN frame (control frames included, as the reference appends
+ * them); its opcode is the last non-zero b0 & 0x0F of the stream so far,
+ * seeded from d_state[j].opcode and never reset between messages.  Message
+ * buffers lie back to back in d_msg (16-byte aligned, msg_cap bytes; wire_len
+ * always suffices) in the order of their FIN frames; d_msgs[0..d_count[0])
+ * describes them (room for n), d_count[1] = bytes used in d_msg.  Frames
+ * after a stream's last FIN frame are its tail: no byte of theirs is written,
+ * d_state[j].consumed says where it begins, and the caller resubmits them at
+ * the head of stream j in its next call with the returned d_state[j].opcode.
+ * Asynchronous on `stream`.  Latched for wsg_sync: a frame error (as
+ * wsg_decode_batch; the frame then counts as an empty non-FIN continuation),
+ * or WSG_ENOMEM when the messages need more than msg_cap bytes: then no byte
+ * of d_msg is written and d_count still holds the size needed.             */
+int wsg_decode_messages(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
+                        const uint64_t* d_frame_start, uint32_t n,
+                        const uint32_t* d_stream_first, uint32_t n_streams,
+                        wsg_stream_state* d_state,
+                        uint8_t* d_msg, uint64_t msg_cap,
+                        wsg_msg* d_msgs, uint64_t* d_count,
+                        wsg_recv_info* d_info, void* stream);
+
 /* ---- batch encode: header pack + mask (PrepareSendFrame over many frames) */
 /* Frames are written back to back into d_wire (16-byte aligned, capacity
  * wire_cap bytes).  d_wire_off[0..n] receives each frame's offset;

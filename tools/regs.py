@@ -1,6 +1,6 @@
 """Register/occupancy report for k_decode and source variants with paths cut
-out (which path sets the kernel's VGPR count).  Compiles for gfx950 only
-(no GPU needed).
+out (which path sets the kernel's VGPR count), and for k_msg_gather
+(wsg_decode_messages).  Compiles for gfx950 only (no GPU needed).
 
 usage: python tools/regs.py
 """
@@ -47,3 +47,4 @@ if __name__ == "__main__":
     report(cut(src, staged), "no-staged")
     report(cut(src, boundary), "no-boundary")
     report(cut(cut(src, staged), boundary), "no-staged-no-boundary")
+    report(src, "k_msg_gather", kernel="_ZN3wsg12k_msg_gather")
