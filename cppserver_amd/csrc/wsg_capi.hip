@@ -915,6 +915,7 @@ struct Knobs {
     int enc_blocks_per_cu = 0;                     // $WSG_ENC_BLOCKS_PER_CU: k_encode_mask grid cap (0: default)
     bool multi_share = false;                      // $WSG_HOST_MULTI_SHARE=1: multi-context splits keep contexts of one device
     uint64_t enc_launch_pieces = 0;                // $WSG_ENC_LAUNCH_PIECES: pieces per k_encode_mask launch
+    int dec_blocks_per_cu = 0;                     // $WSG_DEC_BLOCKS_PER_CU: k_decode grid cap (0: default)
 };
 
 Knobs read_knobs()
@@ -941,6 +942,11 @@ Knobs read_knobs()
     }
     if (const char* e = wsg::envp("WSG_ENC_LAUNCH_PIECES"))     // (tests: split launches)
         k.enc_launch_pieces = std::strtoull(e, nullptr, 10);
+    if (const char* e = wsg::envp("WSG_DEC_BLOCKS_PER_CU")) {   // (tests: several tiles per k_decode block)
+        const int v = std::atoi(e);
+        if (v >= 1 && v <= 4096)
+            k.dec_blocks_per_cu = v;
+    }
     if (const char* e = wsg::envp("WSG_HOST_MULTI_SHARE"))      // (one-GPU tests of the multi-device split)
         k.multi_share = *e == '1';
     return k;
@@ -995,6 +1001,8 @@ int wsg_create(int device, wsg_ctx** out)
     if (k.enc_blocks_per_cu)
         c->enc_blocks_per_cu = k.enc_blocks_per_cu;
     c->enc_launch_pieces = k.enc_launch_pieces;
+    if (k.dec_blocks_per_cu)
+        c->dec_blocks_per_cu = k.dec_blocks_per_cu;
     c->multi_share = k.multi_share;
     *out = c;
     return WSG_OK;

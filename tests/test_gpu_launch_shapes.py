@@ -23,7 +23,7 @@ from cppserver_amd import workloads as wl  # noqa: E402
 
 
 def _codec(**env):
-    keys = ("WSG_ENC_BLOCKS_PER_CU", "WSG_ENC_LAUNCH_PIECES")
+    keys = ("WSG_ENC_BLOCKS_PER_CU", "WSG_ENC_LAUNCH_PIECES", "WSG_DEC_BLOCKS_PER_CU")
     for k in keys:
         os.environ.pop(k, None)
     os.environ.update({k: str(v) for k, v in env.items()})

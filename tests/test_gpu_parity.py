@@ -618,8 +618,11 @@ def test_encode_capacity_error(codec):
 
 
 # ---------------------------------------------------------------- host-staged
-@pytest.mark.parametrize("n,key,phase", [(1, 0xDEADBEEF, 0), (15, 1, 3), (4097, 0xA1B2C3D4, 2), (1 << 20, 7, 1)])
+@pytest.mark.parametrize("n,key,phase", [(1, 0xDEADBEEF, 0), (15, 1, 3), (4097, 0xA1B2C3D4, 2), (1 << 20, 7, 1),
+                                         ((32 << 20) + 4097, 0xA1B2C3D4, 3)])
 def test_xor_host(codec, n, key, phase):
+    if n > 32 << 20:   # past one k_xor grid (32 blocks per CU, 16 bytes per thread): the kernel's grid-stride loop
+        assert n > torch.cuda.get_device_properties(0).multi_processor_count * 32 * 256 * 16
     data = wl.random_bytes(np.random.default_rng(n), n)
     kb = np.frombuffer(int(key).to_bytes(4, "little"), np.uint8)
     exp = data ^ kb[(np.arange(n) + phase) % 4]
