@@ -208,6 +208,12 @@ class Codec:
             stream = self._torch.cuda.current_stream(self.device)
         return ctypes.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream))
 
+    def own_stream(self):
+        """The context's own non-blocking stream (wsg_stream) as a torch
+        stream: pass it as ``stream`` or enter it with torch.cuda.stream().
+        It lives as long as the context."""
+        return self._torch.cuda.ExternalStream(self._L.wsg_stream(self._ctx), device=self.device)
+
     def sync(self, stream=None):
         """Synchronize and raise WSGError on a latched data-dependent error."""
         _check(self._L.wsg_sync(self._ctx, self._stream(stream)), "wsg_sync")

@@ -31,6 +31,15 @@ struct wsg_enc_scratch {
     uint64_t piece_frame_cap = 0;
 };
 
+// The users of one per-context scratch, in the order of their calls: the
+// stream of the last of them and an event recorded behind it, so that a call
+// on another stream waits for it on the device (scratch_enter / scratch_leave).
+struct wsg_scratch_order {
+    hipStream_t last = nullptr;
+    hipEvent_t done = nullptr;   // timing disabled; made by the first call
+    bool recorded = false;
+};
+
 struct wsg_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -68,11 +77,13 @@ struct wsg_ctx {
     unsigned long long* h_err_copy = nullptr;   // page-locked: d_err_host after a large in-place decode
     // scratch
     wsg_enc_scratch enc;
+    wsg_scratch_order enc_order;   // wsg_encode_batch calls
     // wsg_decode_messages: the plan block (wsg::msg_plan_layout) and the gather's piece records
     uint8_t* d_msg_plan = nullptr;
     uint64_t msg_plan_cap = 0;
     wsg::MsgPiece* d_msg_pieces = nullptr;
     uint64_t msg_pieces_cap = 0;
+    wsg_scratch_order msg_order;   // wsg_decode_messages calls
     // staging for host entry points
     uint8_t* d_stage = nullptr;
     uint8_t* h_stage = nullptr;
@@ -186,6 +197,36 @@ int ensure_array(T*& ptr, uint64_t& cap, uint64_t want)
     if (hipMalloc(&ptr, want * sizeof(T)) != hipSuccess)
         return WSG_ENOMEM;
     cap = want;
+    return WSG_OK;
+}
+
+// Before a call on `s` touches the scratch `o` orders: wait on the device for
+// the last call that used it if that ran on another stream (no host
+// synchronisation).  *ordered = false while `s` is capturing: a captured call
+// neither waits nor records (the event would become a node of the graph, and a
+// wait on an event recorded outside the capture is not capturable).
+int scratch_enter(wsg_scratch_order& o, hipStream_t s, bool* ordered)
+{
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    WSG_HIP(hipStreamIsCapturing(s, &cap));
+    *ordered = cap == hipStreamCaptureStatusNone;
+    if (!*ordered)
+        return WSG_OK;
+    if (!o.done)
+        WSG_HIP(hipEventCreateWithFlags(&o.done, hipEventDisableTiming));
+    if (o.recorded && o.last != s)
+        WSG_HIP(hipStreamWaitEvent(s, o.done, 0));
+    return WSG_OK;
+}
+
+// Behind the call's last launch on `s`.
+int scratch_leave(wsg_scratch_order& o, hipStream_t s, bool ordered)
+{
+    if (!ordered)
+        return WSG_OK;
+    WSG_HIP(hipEventRecord(o.done, s));
+    o.last = s;
+    o.recorded = true;
     return WSG_OK;
 }
 
@@ -1036,6 +1077,9 @@ int wsg_destroy(wsg_ctx* c)
     if (c->h_err_copy)
         (void)hipHostFree(c->h_err_copy);
     free_enc(c->enc);
+    for (hipEvent_t ev : {c->enc_order.done, c->msg_order.done})
+        if (ev)
+            (void)hipEventDestroy(ev);
     (void)hipFree(c->d_msg_plan);
     (void)hipFree(c->d_msg_pieces);
     (void)hipFree(c->d_stage);
@@ -1171,15 +1215,20 @@ int wsg_decode_messages(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, co
         return rc;
     wsg::MsgPlan plan;
     wsg::msg_plan_layout(c->d_msg_plan, n, &plan);
+    // the plan block and the piece records are the context's: behind the
+    // previous call's kernels, whatever stream they ran on
+    bool ordered = false;
+    if (int rc = scratch_enter(c->msg_order, s, &ordered))
+        return rc;
     WSG_HIP(wsg::launch_msg_plan(s, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams, d_state, msg_cap,
                                  d_msgs, d_count, d_info, plan, c->d_msg_pieces, pieces_cap, c->d_err));
     if (n == 0)
-        return WSG_OK;
+        return scratch_leave(c->msg_order, s, ordered);
     const int t = timing_begin(c, s);
     WSG_HIP(wsg::launch_msg_gather(s, grid_for(c, ceil_div(pieces_cap, wsg::BLOCK / 64), c->enc_blocks_per_cu), d_wire,
                                    plan, c->d_msg_pieces, pieces_cap, d_msg, msg_cap));
     timing_end(c, s, t);
-    return WSG_OK;
+    return scratch_leave(c->msg_order, s, ordered);
 }
 
 namespace {
@@ -1269,7 +1318,14 @@ int wsg_encode_batch(wsg_ctx* c, const uint8_t* d_payload, const wsg_send_desc* 
     }
     if (int rc = ensure_enc(c, c->enc, n, wire_cap))
         return rc;
-    return encode_launch(c, s, d_payload, d_desc, n, d_wire, wire_cap, d_wire_off, c->enc, c->d_err);
+    // c->enc is the context's: behind the previous call's kernels, whatever
+    // stream they ran on
+    bool ordered = false;
+    if (int rc = scratch_enter(c->enc_order, s, &ordered))
+        return rc;
+    if (int rc = encode_launch(c, s, d_payload, d_desc, n, d_wire, wire_cap, d_wire_off, c->enc, c->d_err))
+        return rc;
+    return scratch_leave(c->enc_order, s, ordered);
 }
 
 namespace {

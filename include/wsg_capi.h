@@ -18,6 +18,23 @@
  *
  * Thread-safety: one wsg_ctx per host thread.  A ctx is not thread-safe.
  *
+ * Streams: one thread may drive a ctx on several streams.  wsg_encode_batch
+ * calls share one scratch of the ctx (scan partials, piece starts, piece ->
+ * frame map) and wsg_decode_messages calls another (plan block, piece
+ * records); wsg_decode_batch and the fan-out calls use none.  The calls that
+ * share a scratch are ordered across streams on the device, in the order they
+ * were made: a call on another stream than the previous one first waits
+ * (hipStreamWaitEvent, no host synchronisation) for an event recorded behind
+ * that one, so two batches double-buffered on two streams run their
+ * wsg_encode_batch kernels one after the other.  A call made while its stream
+ * is capturing is not ordered: it neither waits nor records, so the caller
+ * keeps other users of that scratch off the device while the graph runs.  A
+ * graph holding wsg_encode_batch / wsg_decode_messages launches names the
+ * scratch addresses it was captured with; a later call that needs a larger
+ * scratch frees them (after a device synchronise), and the graph must not be
+ * replayed after that: give such a graph a ctx of its own.  Capture no call
+ * that has to grow a scratch: run it once with the same n and capacity first.
+ *
  * Debug: with $WSG_CHECK=1 at wsg_create, the device entry points check
  * before every launch that each operand range lies inside one device
  * allocation (encode: every descriptor's payload range too, read back from
@@ -88,8 +105,10 @@ typedef struct wsg_ctx wsg_ctx;
 /* Bind to HIP device `device`, create a non-blocking stream, small scratch.   */
 int wsg_create(int device, wsg_ctx** out);
 int wsg_destroy(wsg_ctx* ctx);
-/* Synchronize `stream` (NULL = default stream) and return the first
- * data-dependent error latched since the last wsg_sync (then clear it).      */
+/* Synchronize `stream` (NULL = default stream) and return one data-dependent
+ * error latched since the last wsg_sync (then clear the latch): over all the
+ * calls since then, on any stream, the error of the lowest frame index (the
+ * latch is an atomic minimum of frame << 8 | code), not the first in time.   */
 int wsg_sync(wsg_ctx* ctx, void* stream);
 /* HIP stream owned by the context (a hipStream_t). */
 void* wsg_stream(wsg_ctx* ctx);
