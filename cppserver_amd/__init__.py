@@ -14,9 +14,9 @@ import os
 import numpy as np
 
 from .layout import (  # noqa: F401  (re-exported)
-    CB_CLOSE, CB_PING, CB_PONG, CB_RECEIVED, MSG, RECV_INFO, SEND_DESC, STREAM_STATE, WS_BINARY, WS_CLOSE, WS_FIN,
-    WS_PING, WS_PONG, WS_TEXT, WSG_EHIP, WSG_EINVAL, WSG_ENOMEM, WSG_ETRUNC, WSG_OK, frame_size, frame_sizes,
-    key_from_bytes, message_plan,
+    CB_CLOSE, CB_PING, CB_PONG, CB_RECEIVED, MSG, RECV_INFO, SEND_DESC, STREAM_SPAN, STREAM_STATE, WS_BINARY, WS_CLOSE,
+    WS_FIN, WS_PING, WS_PONG, WS_TEXT, WSG_EHIP, WSG_EINVAL, WSG_ENOMEM, WSG_ETRUNC, WSG_OK, frame_plan, frame_size,
+    frame_sizes, key_from_bytes, message_plan,
 )
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -62,6 +62,9 @@ def lib(path=None):
         "wsg_stream": (vp, [vp]),
         "wsg_decode_batch": (ci, [vp, vp, u64, vp, u32, vp, vp, vp]),
         "wsg_decode_messages": (ci, [vp, vp, u64, vp, u32, vp, u32, vp, vp, u64, vp, vp, vp, vp]),
+        "wsg_frame_streams": (ci, [vp, vp, u64, vp, u32, vp, u32, vp, vp, vp]),
+        "wsg_decode_streams": (ci, [vp, vp, u64, vp, u32, vp, vp, u32, vp, vp, u64, vp, vp, vp, ctypes.POINTER(u32),
+                                    vp]),
         "wsg_encode_batch": (ci, [vp, vp, vp, u32, vp, u64, vp, vp]),
         "wsg_fanout_encode": (ci, [vp, vp, u64, vp, u32, ctypes.c_uint8, ci, vp, u64, vp]),
         "wsg_fanout_encode_many": (ci, [vp, vp, vp, vp, vp, u32, vp, u32, ci, vp, u64, vp, vp]),
@@ -280,6 +283,88 @@ class Codec:
                                          ctypes.c_void_p(info.data_ptr()), self._stream(stream))
         _check(rc, "wsg_decode_messages")
         return msg, msgs, count, state, info
+
+    # -- the device framer (raw stream bytes -> frame table -> messages) ------
+    def _frame_args(self, what, wire, spans, frame_start, frame_cap, stream_first):
+        t = self._torch
+        ns = int(spans.numel()) // STREAM_SPAN.itemsize
+        if spans.element_size() != 1 or int(spans.numel()) != ns * STREAM_SPAN.itemsize:
+            raise WSGError(WSG_EINVAL, "%s: spans must be uint8, n_streams * 32 bytes" % what)
+        dev = wire.device
+        if frame_cap is None:   # every frame has at least two bytes
+            frame_cap = int(wire.numel()) // 2 if frame_start is None else int(frame_start.numel())
+        cap = int(frame_cap)
+        if frame_start is None:
+            frame_start = t.empty(max(cap, 1), dtype=t.int64, device=dev)
+        if stream_first is None:
+            stream_first = t.empty(ns + 1, dtype=t.int32, device=dev)
+        if (cap > int(frame_start.numel()) or frame_start.element_size() != 8 or stream_first.element_size() != 4
+                or int(stream_first.numel()) < ns + 1 or cap > 0xFFFFFFFF):
+            raise WSGError(WSG_EINVAL, "%s: a buffer is smaller than the batch needs" % what)
+        return ns, cap, frame_start, stream_first
+
+    def frame_streams(self, wire, spans, frame_start=None, frame_cap=None, stream_first=None, count=None,
+                      stream=None):
+        """wsg_frame_streams: the frame boundaries of the streams ``spans``
+        (uint8 CUDA tensor of n_streams * 32 bytes, STREAM_SPAN: off and len
+        in, consumed and need out, in place) of ``wire``.  Returns
+        (frame_start, stream_first, count): int64[frame_cap] wire offsets
+        (count[0] valid), int32[n_streams + 1] and count int64[2] = [frames,
+        bytes in whole frames].  ``frame_cap`` defaults to the room of
+        ``frame_start``, or to wire bytes / 2, which always suffices."""
+        t = self._torch
+        ns, cap, frame_start, stream_first = self._frame_args("frame_streams", wire, spans, frame_start, frame_cap,
+                                                              stream_first)
+        if count is None:
+            count = t.empty(2, dtype=t.int64, device=wire.device)
+        rc = self._L.wsg_frame_streams(self._ctx, ctypes.c_void_p(wire.data_ptr()), wire.numel(),
+                                       ctypes.c_void_p(spans.data_ptr()), ns,
+                                       ctypes.c_void_p(frame_start.data_ptr()), cap,
+                                       ctypes.c_void_p(stream_first.data_ptr()), ctypes.c_void_p(count.data_ptr()),
+                                       self._stream(stream))
+        _check(rc, "wsg_frame_streams")
+        return frame_start, stream_first, count
+
+    def decode_streams(self, wire, spans, state=None, frame_start=None, frame_cap=None, stream_first=None,
+                       msg=None, msg_cap=None, stream=None, msgs=None, count=None, info=None):
+        """wsg_decode_streams: frame_streams, then decode_messages over the
+        frames it found (one stream synchronisation between the two), then
+        every span's consumed lowered to the stream's first tail frame.
+        ``spans`` as frame_streams, ``state`` / ``msg`` / ``msg_cap`` /
+        ``msgs`` / ``count`` / ``info`` as decode_messages with room for
+        ``frame_cap`` frames (the default, wire bytes / 2, makes ``msgs`` and
+        ``info`` 36 times the wire: give a ``frame_cap`` for anything large).
+        Returns (msg, msgs, count, state, info, frame_start, stream_first,
+        n_frames)."""
+        t = self._torch
+        ns, cap, frame_start, stream_first = self._frame_args("decode_streams", wire, spans, frame_start, frame_cap,
+                                                              stream_first)
+        dev = wire.device
+        if state is None:
+            state = t.zeros(max(ns, 1) * STREAM_STATE.itemsize, dtype=t.uint8, device=dev)
+        if msg_cap is None:
+            msg_cap = int(wire.numel()) if msg is None else int(msg.numel())
+        mcap = int(msg_cap)
+        if msg is None:
+            msg = t.empty(max(mcap, 16), dtype=t.uint8, device=dev)
+        if msgs is None:
+            msgs = t.empty(max(cap, 1) * MSG.itemsize, dtype=t.uint8, device=dev)
+        if count is None:
+            count = t.empty(2, dtype=t.int64, device=dev)
+        if info is None:
+            info = t.empty(max(cap, 1) * RECV_INFO.itemsize, dtype=t.uint8, device=dev)
+        if (mcap > int(msg.numel()) or int(state.numel()) < ns * STREAM_STATE.itemsize
+                or int(msgs.numel()) < cap * MSG.itemsize or int(info.numel()) < cap * RECV_INFO.itemsize):
+            raise WSGError(WSG_EINVAL, "decode_streams: a buffer is smaller than the batch needs")
+        n = ctypes.c_uint32()
+        rc = self._L.wsg_decode_streams(self._ctx, ctypes.c_void_p(wire.data_ptr()), wire.numel(),
+                                        ctypes.c_void_p(spans.data_ptr()), ns, ctypes.c_void_p(state.data_ptr()),
+                                        ctypes.c_void_p(frame_start.data_ptr()), cap,
+                                        ctypes.c_void_p(stream_first.data_ptr()), ctypes.c_void_p(msg.data_ptr()),
+                                        mcap, ctypes.c_void_p(msgs.data_ptr()), ctypes.c_void_p(count.data_ptr()),
+                                        ctypes.c_void_p(info.data_ptr()), ctypes.byref(n), self._stream(stream))
+        _check(rc, "wsg_decode_streams")
+        return msg, msgs, count, state, info, frame_start, stream_first, n.value
 
     def prepare_decode(self, wire, frame_start, out, info, stream=None):
         """wsg_decode_batch on fixed buffers (a server's batch arena), with

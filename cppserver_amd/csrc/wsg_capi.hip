@@ -84,6 +84,10 @@ struct wsg_ctx {
     wsg::MsgPiece* d_msg_pieces = nullptr;
     uint64_t msg_pieces_cap = 0;
     wsg_scratch_order msg_order;   // wsg_decode_messages calls
+    // wsg_frame_streams: per-stream counts and scan partials (wsg::frame_plan_layout)
+    uint64_t* d_frame_plan = nullptr;
+    uint64_t frame_plan_cap = 0;
+    wsg_scratch_order frame_order;   // wsg_frame_streams calls
     // staging for host entry points
     uint8_t* d_stage = nullptr;
     uint8_t* h_stage = nullptr;
@@ -1077,9 +1081,10 @@ int wsg_destroy(wsg_ctx* c)
     if (c->h_err_copy)
         (void)hipHostFree(c->h_err_copy);
     free_enc(c->enc);
-    for (hipEvent_t ev : {c->enc_order.done, c->msg_order.done})
+    for (hipEvent_t ev : {c->enc_order.done, c->msg_order.done, c->frame_order.done})
         if (ev)
             (void)hipEventDestroy(ev);
+    (void)hipFree(c->d_frame_plan);
     (void)hipFree(c->d_msg_plan);
     (void)hipFree(c->d_msg_pieces);
     (void)hipFree(c->d_stage);
@@ -1229,6 +1234,78 @@ int wsg_decode_messages(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, co
                                    plan, c->d_msg_pieces, pieces_cap, d_msg, msg_cap));
     timing_end(c, s, t);
     return scratch_leave(c->msg_order, s, ordered);
+}
+
+// The device framer: two walks over every stream (one wave each) with a scan
+// of the per-stream frame counts between them.
+int wsg_frame_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_stream_span* d_span,
+                      uint32_t n_streams, uint64_t* d_frame_start, uint32_t frame_cap, uint32_t* d_stream_first,
+                      uint64_t* d_count, void* stream)
+{
+    if (!c || !d_count || !d_stream_first || (wire_len && !d_wire) || (n_streams && !d_span) ||
+        (frame_cap && !d_frame_start) || n_streams == UINT32_MAX)
+        return WSG_EINVAL;
+    if (!aligned16(d_wire))
+        return WSG_EINVAL;
+    if (c->check &&
+        (!in_alloc(d_wire, (wire_len + 15) & ~uint64_t(15)) ||
+         !in_alloc(d_span, uint64_t(n_streams) * sizeof(wsg_stream_span)) ||
+         !in_alloc(d_frame_start, uint64_t(frame_cap) * 8) ||
+         !in_alloc(d_stream_first, (uint64_t(n_streams) + 1) * 4) || !in_alloc(d_count, 2 * 8)))
+        return WSG_EINVAL;
+    hipStream_t s = pick(c, stream);
+    if (int rc = ensure_array(c->d_frame_plan, c->frame_plan_cap, wsg::frame_plan_layout(nullptr, n_streams, nullptr)))
+        return rc;
+    wsg::FramePlan plan;
+    wsg::frame_plan_layout(c->d_frame_plan, n_streams, &plan);
+    // the counts and partials are the context's: behind the previous call's
+    // kernels, whatever stream they ran on
+    bool ordered = false;
+    if (int rc = scratch_enter(c->frame_order, s, &ordered))
+        return rc;
+    const int t = n_streams ? timing_begin(c, s) : -1;
+    WSG_HIP(wsg::launch_frame_streams(s, grid_for(c, ceil_div(n_streams, wsg::BLOCK / 64), c->dec_blocks_per_cu), d_wire,
+                                      wire_len, d_span, n_streams, d_frame_start, frame_cap, d_stream_first, d_count,
+                                      plan, c->d_err));
+    timing_end(c, s, t);
+    return scratch_leave(c->frame_order, s, ordered);
+}
+
+int wsg_decode_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_stream_span* d_span,
+                       uint32_t n_streams, wsg_stream_state* d_state, uint64_t* d_frame_start, uint32_t frame_cap,
+                       uint32_t* d_stream_first, uint8_t* d_msg, uint64_t msg_cap, wsg_msg* d_msgs, uint64_t* d_count,
+                       wsg_recv_info* d_info, uint32_t* n_frames_out, void* stream)
+{
+    if (!c || !n_frames_out || !d_count || (n_streams && !d_state) || (msg_cap && !d_msg) ||
+        (frame_cap && (!d_msgs || !d_info)) || !aligned16(d_msg))
+        return WSG_EINVAL;
+    if (c->check && (!in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) || !in_alloc(d_msg, msg_cap) ||
+                     !in_alloc(d_msgs, uint64_t(frame_cap) * sizeof(wsg_msg)) ||
+                     !in_alloc(d_info, uint64_t(frame_cap) * sizeof(wsg_recv_info))))
+        return WSG_EINVAL;
+    hipStream_t s = pick(c, stream);
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    WSG_HIP(hipStreamIsCapturing(s, &cap));
+    if (cap != hipStreamCaptureStatusNone)
+        return WSG_EINVAL;   // the frame count is read on the host in the middle
+    *n_frames_out = 0;
+    if (int rc = wsg_frame_streams(c, d_wire, wire_len, d_span, n_streams, d_frame_start, frame_cap, d_stream_first,
+                                   d_count, stream))
+        return rc;
+    uint64_t found = 0;
+    WSG_HIP(hipMemcpyAsync(&found, d_count, sizeof(found), hipMemcpyDeviceToHost, s));
+    WSG_HIP(hipStreamSynchronize(s));
+    if (found > uint64_t(UINT32_MAX) - 1)
+        return WSG_EINVAL;
+    if (found > frame_cap)
+        return WSG_ENOMEM;
+    const uint32_t n = uint32_t(found);
+    *n_frames_out = n;
+    if (int rc = wsg_decode_messages(c, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams, d_state, d_msg,
+                                     msg_cap, d_msgs, d_count, d_info, stream))
+        return rc;
+    WSG_HIP(wsg::launch_frame_tail(s, d_span, n_streams, d_frame_start, d_stream_first, d_state, n));
+    return WSG_OK;
 }
 
 namespace {

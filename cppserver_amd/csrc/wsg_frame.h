@@ -67,6 +67,11 @@ WSG_HD uint8_t header_byte(uint8_t opcode, bool mask, uint64_t body, uint32_t ke
     return key_byte(key, r - 2u - ext);                          // mask key bytes
 }
 
+// Extended-length bytes the second header byte announces (ws.cpp:331/349/367).
+WSG_HD uint32_t header_ext(uint8_t b1) { return (b1 & 0x7F) == 126 ? 2u : (b1 & 0x7F) == 127 ? 8u : 0u; }
+// Header length, known from the second byte alone: 2/4/10 (+4 when masked).
+WSG_HD uint32_t header_len(uint8_t b1) { return 2u + header_ext(b1) + 4u * ((b1 >> 7) & 1u); }
+
 // Parse a complete header at h[0..avail).  Returns 0 or WSG_ETRUNC.
 // Matches ws.cpp:320-386 for a header delivered whole.
 template <class Load>
@@ -75,9 +80,9 @@ WSG_HD int parse_header(Load byte_at, uint64_t avail, wsg_recv_info& r)
     if (avail < 2)
         return WSG_ETRUNC;
     const uint8_t b0 = byte_at(0), b1 = byte_at(1);
-    const uint32_t ext = (b1 & 0x7F) == 126 ? 2u : (b1 & 0x7F) == 127 ? 8u : 0u;
+    const uint32_t ext = header_ext(b1);
     const uint32_t masked = (b1 >> 7) & 1u;
-    const uint32_t hdr = 2u + ext + 4u * masked;
+    const uint32_t hdr = header_len(b1);
     if (avail < hdr)
         return WSG_ETRUNC;
     uint64_t len = b1 & 0x7F;

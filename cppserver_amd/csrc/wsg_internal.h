@@ -116,6 +116,31 @@ hipError_t launch_msg_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_len
 hipError_t launch_msg_gather(hipStream_t s, int grid, const uint8_t* wire, const MsgPlan& plan,
                              const MsgPiece* pieces, uint64_t pieces_cap, uint8_t* msg, uint64_t msg_cap);
 
+// ---- the device framer (wsg_frame_streams) ---------------------------------
+// Scratch of one call, carved out of one device array of uint64 (one block =
+// BLOCK streams).
+struct FramePlan {
+    uint64_t* cnt;     // ns: whole frames of each stream (k_frame_count)
+    uint64_t* ex;      // ns: block-local exclusive prefix of cnt
+    uint64_t* bcnt;    // nb: block sums of cnt
+    uint64_t* bpre;    // nb: their exclusive prefixes
+    uint64_t* bcons;   // nb: block sums of the spans' consumed bytes
+    uint64_t* tot;     // [0] frames found, [1] bytes consumed
+};
+// Entries of that array for ns streams; plan (or null) gets the pointers into base.
+uint64_t frame_plan_layout(uint64_t* base, uint32_t ns, FramePlan* plan);
+// Count walk, scan, write walk: the spans' consumed / need, stream_first
+// (ns + 1), count, and, when they fit, the frame_start entries; latches span
+// and capacity errors.  grid: blocks of the two walks (one wave per stream,
+// grid-stride).
+hipError_t launch_frame_streams(hipStream_t s, int grid, const uint8_t* wire, uint64_t wire_len, wsg_stream_span* span,
+                                uint32_t ns, uint64_t* frame_start, uint32_t frame_cap, uint32_t* stream_first,
+                                uint64_t* count, const FramePlan& plan, unsigned long long* err);
+// wsg_decode_streams: every span's consumed lowered to the start of the
+// stream's first frame that wsg_decode_messages left in the tail.
+hipError_t launch_frame_tail(hipStream_t s, wsg_stream_span* span, uint32_t ns, const uint64_t* frame_start,
+                             const uint32_t* stream_first, const wsg_stream_state* state, uint32_t n);
+
 // Messages of one fan-out launch (blockIdx.y): payload and output offsets.
 constexpr int FAN_MSGS = 32;
 struct FanMsgs {

@@ -1,8 +1,8 @@
 """Record layouts shared by the C-ABI (include/wsg_capi.h) and its callers.
 
 numpy structured dtypes whose byte layout is exactly ``wsg_send_desc``,
-``wsg_recv_info``, ``wsg_msg`` and ``wsg_stream_state``; importing this module
-loads no native code.
+``wsg_recv_info``, ``wsg_msg``, ``wsg_stream_state`` and ``wsg_stream_span``;
+importing this module loads no native code.
 """
 import numpy as np
 
@@ -60,6 +60,11 @@ STREAM_STATE = np.dtype([("consumed", "<u4"), ("opcode", "u1"), ("_pad", "u1", (
 
 assert MSG.itemsize == 40 and STREAM_STATE.itemsize == 8
 
+# wsg_stream_span: one connection's bytes in a wsg_frame_streams batch.
+STREAM_SPAN = np.dtype([("off", "<u8"), ("len", "<u8"), ("consumed", "<u8"), ("need", "<u8")])
+
+assert STREAM_SPAN.itemsize == 32
+
 # Opcode byte values (reference include/server/ws/ws.h:33-43).
 WS_FIN, WS_TEXT, WS_BINARY, WS_CLOSE, WS_PING, WS_PONG = 0x80, 0x01, 0x02, 0x08, 0x09, 0x0A
 
@@ -92,6 +97,74 @@ def frame_sizes(desc):
     body = length + np.where(prefix, 2, 0).astype(np.uint64)
     hdr = np.where(body < 126, 2, np.where(body < 65536, 4, 10)).astype(np.uint64)
     return hdr + np.where(desc["mask"] != 0, 4, 0).astype(np.uint64) + body
+
+
+U64_MAX = 2**64 - 1
+
+
+def bad_spans(wire_len, spans):
+    """Which spans wsg_frame_streams refuses (WSG_EINVAL, no frames): one that
+    runs past the wire, or that starts before the end of the span before it
+    where that one lies inside the wire."""
+    spans = np.asarray(spans, dtype=STREAM_SPAN)
+    bad = np.zeros(len(spans), dtype=bool)
+    prev_end = None                                   # end of span j - 1 if it lies inside the wire
+    for j in range(len(spans)):
+        off, length = int(spans["off"][j]), int(spans["len"][j])
+        inside = off + length <= wire_len             # Python integers: no wrap
+        bad[j] = not inside or (prev_end is not None and off < prev_end)
+        prev_end = off + length if inside else None
+    return bad
+
+
+def frame_plan(wire, spans):
+    """wsg_frame_streams restated on the host over wsg_header_unpack: the
+    whole frames of every stream ``wire[off, off + len)``.
+
+    ``spans``: STREAM_SPAN records (off and len are read).  Returns
+    (frame_start, stream_first, spans_out, count): the frames' wire offsets
+    (uint64), the exclusive prefix of the streams' frame counts (n_streams +
+    1), the spans with consumed and need filled in, and count = [frames, sum
+    of consumed].  A refused span (bad_spans) has no frames, consumed 0 and
+    need 0."""
+    from . import _np_ptr, lib                        # the ABI's host parser; importing layout loads nothing
+
+    unpack = lib().wsg_header_unpack
+    wire = np.ascontiguousarray(wire, dtype=np.uint8)
+    data = wire.tobytes()
+    out = np.array(np.asarray(spans, dtype=STREAM_SPAN), copy=True)
+    out["consumed"] = 0
+    out["need"] = 0
+    bad = bad_spans(len(data), out)
+    info = np.zeros(1, dtype=RECV_INFO)
+    info_p = _np_ptr(info)
+    starts, first = [], [0]
+    for j in range(len(out)):
+        pos = int(out["off"][j])
+        end = pos + int(out["len"][j])
+        need = 0
+        while not bad[j]:
+            rem = end - pos
+            if rem < 2:
+                need = 2 if rem else 0
+                break
+            head = data[pos: min(pos + 14, end)]
+            if unpack(head, len(head), info_p) != 0:  # incomplete: its length is known from the second byte
+                assert unpack(head + bytes(14 - len(head)), 14, info_p) == 0
+                need = int(info["hdr_len"][0])
+                break
+            size = int(info["hdr_len"][0]) + int(info["len"][0])
+            if size > rem:
+                need = min(size, U64_MAX)
+                break
+            starts.append(pos)
+            pos += size
+        if not bad[j]:
+            out["consumed"][j] = pos - int(out["off"][j])
+            out["need"][j] = need
+        first.append(len(starts))
+    count = np.array([len(starts), int(out["consumed"].astype(object).sum())], dtype=np.uint64)
+    return np.array(starts, dtype=np.uint64), np.array(first, dtype=np.uint64), out, count
 
 
 def message_plan(info, stream_first, state=None, payload=None):

@@ -20,8 +20,10 @@
  *
  * Streams: one thread may drive a ctx on several streams.  wsg_encode_batch
  * calls share one scratch of the ctx (scan partials, piece starts, piece ->
- * frame map) and wsg_decode_messages calls another (plan block, piece
- * records); wsg_decode_batch and the fan-out calls use none.  The calls that
+ * frame map), wsg_decode_messages calls another (plan block, piece records)
+ * and wsg_frame_streams calls a third (per-stream frame counts, scan
+ * partials; wsg_decode_streams is one call of each of the last two);
+ * wsg_decode_batch and the fan-out calls use none.  The calls that
  * share a scratch are ordered across streams on the device, in the order they
  * were made: a call on another stream than the previous one first waits
  * (hipStreamWaitEvent, no host synchronisation) for an event recorded behind
@@ -29,7 +31,8 @@
  * wsg_encode_batch kernels one after the other.  A call made while its stream
  * is capturing is not ordered: it neither waits nor records, so the caller
  * keeps other users of that scratch off the device while the graph runs.  A
- * graph holding wsg_encode_batch / wsg_decode_messages launches names the
+ * graph holding wsg_encode_batch / wsg_decode_messages / wsg_frame_streams
+ * launches (wsg_decode_streams synchronises and cannot be captured) names the
  * scratch addresses it was captured with; a later call that needs a larger
  * scratch frees them (after a device synchronise), and the graph must not be
  * replayed after that: give such a graph a ctx of its own.  Capture no call
@@ -182,6 +185,86 @@ int wsg_decode_messages(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
                         uint8_t* d_msg, uint64_t msg_cap,
                         wsg_msg* d_msgs, uint64_t* d_count,
                         wsg_recv_info* d_info, void* stream);
+
+/* ---- the device framer: raw stream bytes to a frame table ----------------- */
+/* (Added without an ABI bump, as wsg_decode_messages was: symbols and structs
+ * only.)  One connection's bytes in a batch. */
+typedef struct wsg_stream_span {
+    uint64_t off;       /* in:  wire offset of the stream's first unparsed byte        */
+    uint64_t len;       /* in:  bytes of this stream in the batch                      */
+    uint64_t consumed;  /* out: bytes covered by whole frames (resubmit from off+consumed) */
+    uint64_t need;      /* out: size the partial frame at the tail is known to have    */
+} wsg_stream_span;      /* 32 bytes */
+
+/* Find the frame boundaries of n_streams connections on the device: the
+ * d_frame_start / d_stream_first tables wsg_decode_batch and
+ * wsg_decode_messages take, without a host framer.
+ * Whole frames.  Stream j is d_wire[off, off + len).  Its frames are parsed
+ * from `off`, each header exactly as one delivered whole (wsg_header_unpack,
+ * ws.cpp:320-386).  A frame is whole when its header is complete and hdr_len +
+ * payload length fits in the bytes that remain (compared without forming a sum
+ * that could wrap); the walk stops at the first frame that is not.
+ * consumed: the bytes of the stream's whole frames.
+ * need, with rem = len - consumed: 0 when rem == 0; 2 when rem == 1; the
+ * header's length (known from its second byte) while the header is
+ * incomplete; hdr_len + payload length, saturating at UINT64_MAX, once it is
+ * complete.  The 127 form is taken as the reference takes it, all 64 bits, no
+ * MSB check: a length of 2^63 or 2^64 - 1 is a frame that never completes, not
+ * an error.
+ * Outputs.  d_stream_first[0..n_streams]: the exclusive prefix of the streams'
+ * frame counts ([n_streams] = frames found).  d_frame_start[d_stream_first[j]
+ * ..): stream j's frame starts, absolute wire offsets (frame_cap entries of
+ * room).  d_count[0] = frames found, d_count[1] = the sum of `consumed`.
+ * Span order.  Spans are given in increasing, non-overlapping wire order, so
+ * the table is strictly increasing, as wsg_decode_batch requires; bytes
+ * between spans and partial tails are gaps, which both decode calls allow.
+ * Latched for wsg_sync, under the key stream << 8 | code (the same atomic
+ * minimum, the stream index where the decodes put the frame index):
+ * WSG_EINVAL for a span that runs past wire_len, or that starts before the
+ * end of the span before it (when that one lies inside the wire): that stream
+ * yields no frames, consumed 0 and need 0, the other streams are unaffected;
+ * WSG_ENOMEM for more than frame_cap frames: d_count, d_stream_first and the
+ * spans are still written, not one entry of d_frame_start is; WSG_EINVAL for
+ * more than UINT32_MAX - 1 frames (likewise; d_stream_first saturates).  The
+ * last two are latched under the key n_streams << 8 | code.
+ * Arguments.  d_wire 16-byte aligned and readable to the end of its last
+ * 16-byte block, as for wsg_decode_batch; span offsets of any alignment;
+ * n_streams == 0 is valid (d_stream_first[0] = 0, d_count = {0, 0}).
+ * Asynchronous on `stream`.
+ * Relation to SURVEY Q7.  A stream is parsed as if it arrived unsplit, and a
+ * tail is resubmitted from off + consumed, never continued in the middle of a
+ * header: this is the whole-frame contract wsg_decode_batch already has, not
+ * the reference's mis-parse of a header split across two reads (which
+ * wsg_rx_feed reproduces).
+ * Streams: the calls share a scratch of the ctx (per-stream counts, scan
+ * partials) and are ordered across streams on the device like the
+ * wsg_encode_batch and wsg_decode_messages calls (see "Streams" above), with
+ * the same capture rule: a captured call is not ordered, and a call that has
+ * to grow the scratch must not be captured: run it once with the same
+ * n_streams first.                                                          */
+int wsg_frame_streams(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
+                      wsg_stream_span* d_span, uint32_t n_streams,
+                      uint64_t* d_frame_start, uint32_t frame_cap,
+                      uint32_t* d_stream_first, uint64_t* d_count, void* stream);
+
+/* Raw bytes to messages: wsg_frame_streams, one synchronisation of `stream`
+ * to read the frame count (*n_frames_out), wsg_decode_messages with that n.
+ * d_msgs and d_info need room for frame_cap records; d_count ends as
+ * wsg_decode_messages leaves it (messages, bytes of d_msg).  Then
+ * d_span[j].consumed is lowered to the start of stream j's first tail frame
+ * (the first frame behind the stream's last FIN frame that went into a
+ * message; `need` is left as the framer wrote it), so a connection's whole
+ * carry-over to its next call is: the bytes from off + consumed, and
+ * d_state[j].opcode.  Returns WSG_EINVAL while `stream` is capturing;
+ * WSG_ENOMEM (WSG_EINVAL), with nothing decoded, when the framer found more
+ * than frame_cap (UINT32_MAX - 1) frames (the latch holds it too).  Errors of
+ * single spans and frames are latched as by the two calls.                  */
+int wsg_decode_streams(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
+                       wsg_stream_span* d_span, uint32_t n_streams,
+                       wsg_stream_state* d_state,
+                       uint64_t* d_frame_start, uint32_t frame_cap, uint32_t* d_stream_first,
+                       uint8_t* d_msg, uint64_t msg_cap, wsg_msg* d_msgs, uint64_t* d_count,
+                       wsg_recv_info* d_info, uint32_t* n_frames_out, void* stream);
 
 /* ---- batch encode: header pack + mask (PrepareSendFrame over many frames) */
 /* Frames are written back to back into d_wire (16-byte aligned, capacity

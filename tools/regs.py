@@ -48,3 +48,5 @@ if __name__ == "__main__":
     report(cut(src, boundary), "no-boundary")
     report(cut(cut(src, staged), boundary), "no-staged-no-boundary")
     report(src, "k_msg_gather", kernel="_ZN3wsg12k_msg_gather")
+    report(src, "k_frame_count", kernel="_ZN3wsg13k_frame_count")
+    report(src, "k_frame_write", kernel="_ZN3wsg13k_frame_write")
