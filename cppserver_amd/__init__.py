@@ -14,9 +14,9 @@ import os
 import numpy as np
 
 from .layout import (  # noqa: F401  (re-exported)
-    CB_CLOSE, CB_PING, CB_PONG, CB_RECEIVED, MSG, RECV_INFO, SEND_DESC, STREAM_SPAN, STREAM_STATE, WS_BINARY, WS_CLOSE,
-    WS_FIN, WS_PING, WS_PONG, WS_TEXT, WSG_EHIP, WSG_EINVAL, WSG_ENOMEM, WSG_ETRUNC, WSG_OK, frame_plan, frame_size,
-    frame_sizes, key_from_bytes, message_plan,
+    CB_CLOSE, CB_PING, CB_PONG, CB_RECEIVED, ECHO_REPLY, MSG, RECV_INFO, REPLY_SAME, SEND_DESC, STREAM_SPAN,
+    STREAM_STATE, WS_BINARY, WS_CLOSE, WS_FIN, WS_PING, WS_PONG, WS_TEXT, WSG_EHIP, WSG_EINVAL, WSG_ENOMEM, WSG_ETRUNC,
+    WSG_OK, frame_plan, frame_size, frame_sizes, key_from_bytes, message_plan, reply_plan,
 )
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -65,6 +65,9 @@ def lib(path=None):
         "wsg_frame_streams": (ci, [vp, vp, u64, vp, u32, vp, u32, vp, vp, vp]),
         "wsg_decode_streams": (ci, [vp, vp, u64, vp, u32, vp, vp, u32, vp, vp, u64, vp, vp, vp, ctypes.POINTER(u32),
                                     vp]),
+        "wsg_reply_messages": (ci, [vp, vp, u64, vp, u32, vp, u32, vp, vp, ci, vp, vp, u64, vp, vp, vp, vp, vp, vp]),
+        "wsg_reply_streams": (ci, [vp, vp, u64, vp, u32, vp, vp, u32, vp, vp, ci, vp, vp, u64, vp, vp, vp, vp, vp,
+                                   ctypes.POINTER(u32), vp]),
         "wsg_encode_batch": (ci, [vp, vp, vp, u32, vp, u64, vp, vp]),
         "wsg_fanout_encode": (ci, [vp, vp, u64, vp, u32, ctypes.c_uint8, ci, vp, u64, vp]),
         "wsg_fanout_encode_many": (ci, [vp, vp, vp, vp, vp, u32, vp, u32, ci, vp, u64, vp, vp]),
@@ -365,6 +368,97 @@ class Codec:
                                         ctypes.c_void_p(info.data_ptr()), ctypes.byref(n), self._stream(stream))
         _check(rc, "wsg_decode_streams")
         return msg, msgs, count, state, info, frame_start, stream_first, n.value
+
+    # -- replies (frames -> messages -> frames to send, payload moved once) ----
+    def _reply_args(self, what, wire, n, ns, reply_op, send_keys, reply, reply_cap, reply_off, stream_reply, state,
+                    msgs, count, info):
+        t = self._torch
+        dev = wire.device
+        rule = bytes(int(x) for x in reply_op)
+        if len(rule) != 5:
+            raise WSGError(WSG_EINVAL, "%s: reply_op must hold five bytes (indexed by CB_*)" % what)
+        if send_keys is not None and (send_keys.element_size() != 4 or int(send_keys.numel()) < ns):
+            raise WSGError(WSG_EINVAL, "%s: send_keys must hold n_streams 32-bit keys" % what)
+        if reply_cap is None:   # a reply adds at most 16 bytes to its data, every frame spent 2 on its header
+            reply_cap = int(wire.numel()) + 14 * n if reply is None else int(reply.numel())
+        cap = int(reply_cap)
+        if reply is None:
+            reply = t.empty(max(cap, 16), dtype=t.uint8, device=dev)
+        if reply_off is None:
+            reply_off = t.empty(n + 1, dtype=t.int64, device=dev)
+        if stream_reply is None:
+            stream_reply = t.empty(ns + 1, dtype=t.int64, device=dev)
+        if state is None:
+            state = t.zeros(max(ns, 1) * STREAM_STATE.itemsize, dtype=t.uint8, device=dev)
+        if msgs is None:
+            msgs = t.empty(max(n, 1) * MSG.itemsize, dtype=t.uint8, device=dev)
+        if count is None:
+            count = t.empty(4, dtype=t.int64, device=dev)
+        if info is None:
+            info = t.empty(max(n, 1) * RECV_INFO.itemsize, dtype=t.uint8, device=dev)
+        if (cap > int(reply.numel()) or int(reply_off.numel()) < n + 1 or reply_off.element_size() != 8
+                or int(stream_reply.numel()) < ns + 1 or stream_reply.element_size() != 8
+                or int(count.numel()) < 4 or count.element_size() != 8
+                or int(state.numel()) < ns * STREAM_STATE.itemsize or int(msgs.numel()) < n * MSG.itemsize
+                or int(info.numel()) < n * RECV_INFO.itemsize):
+            raise WSGError(WSG_EINVAL, "%s: a buffer is smaller than the batch needs" % what)
+        return rule, cap, reply, reply_off, stream_reply, state, msgs, count, info
+
+    def reply_messages(self, wire, frame_start, stream_first, reply_op=ECHO_REPLY, mask=False, send_keys=None,
+                       state=None, reply=None, reply_cap=None, stream=None, reply_off=None, stream_reply=None,
+                       msgs=None, count=None, info=None):
+        """wsg_reply_messages: the frames of ``wire`` as decode_messages takes
+        them, answered: ``reply_op`` (five bytes by CB_*: 0 none, REPLY_SAME,
+        or the reply's first header byte), ``mask``, ``send_keys`` (int32 CUDA
+        tensor, one little-endian key per stream; None: all 0).  Returns
+        (reply, reply_off, stream_reply, msgs, count, state, info): the reply
+        frames back to back, int64[n + 1] offsets per message (count[0] + 1
+        valid), int64[n_streams + 1] offsets per stream, the MSG table bytes,
+        count int64[4] = [messages, bytes of the dense layout, reply bytes,
+        reply frames], the new state and the RECV_INFO bytes.  ``reply_cap``
+        defaults to wire bytes + 14 * n, which always suffices."""
+        n = int(frame_start.numel())
+        ns = int(stream_first.numel()) - 1
+        if ns < 0 or stream_first.element_size() != 4:
+            raise WSGError(WSG_EINVAL, "reply_messages: stream_first must hold n_streams + 1 32-bit indices")
+        rule, cap, reply, reply_off, stream_reply, state, msgs, count, info = self._reply_args(
+            "reply_messages", wire, n, ns, reply_op, send_keys, reply, reply_cap, reply_off, stream_reply, state, msgs,
+            count, info)
+        p = ctypes.c_void_p
+        rc = self._L.wsg_reply_messages(self._ctx, p(wire.data_ptr()), wire.numel(), p(frame_start.data_ptr()), n,
+                                        p(stream_first.data_ptr()), ns, p(state.data_ptr()), rule, 1 if mask else 0,
+                                        p(send_keys.data_ptr()) if send_keys is not None else None,
+                                        p(reply.data_ptr()), cap, p(reply_off.data_ptr()), p(stream_reply.data_ptr()),
+                                        p(msgs.data_ptr()), p(count.data_ptr()), p(info.data_ptr()),
+                                        self._stream(stream))
+        _check(rc, "wsg_reply_messages")
+        return reply, reply_off, stream_reply, msgs, count, state, info
+
+    def reply_streams(self, wire, spans, reply_op=ECHO_REPLY, mask=False, send_keys=None, state=None,
+                      frame_start=None, frame_cap=None, stream_first=None, reply=None, reply_cap=None, stream=None,
+                      reply_off=None, stream_reply=None, msgs=None, count=None, info=None):
+        """wsg_reply_streams: frame_streams, then reply_messages over the
+        frames it found (one stream synchronisation between the two), then
+        every span's consumed lowered to the stream's first tail frame.
+        Arguments as decode_streams and reply_messages, with room for
+        ``frame_cap`` frames.  Returns (reply, reply_off, stream_reply, msgs,
+        count, state, info, frame_start, stream_first, n_frames)."""
+        ns, fcap, frame_start, stream_first = self._frame_args("reply_streams", wire, spans, frame_start, frame_cap,
+                                                               stream_first)
+        rule, cap, reply, reply_off, stream_reply, state, msgs, count, info = self._reply_args(
+            "reply_streams", wire, fcap, ns, reply_op, send_keys, reply, reply_cap, reply_off, stream_reply, state,
+            msgs, count, info)
+        n = ctypes.c_uint32()
+        p = ctypes.c_void_p
+        rc = self._L.wsg_reply_streams(self._ctx, p(wire.data_ptr()), wire.numel(), p(spans.data_ptr()), ns,
+                                       p(state.data_ptr()), p(frame_start.data_ptr()), fcap,
+                                       p(stream_first.data_ptr()), rule, 1 if mask else 0,
+                                       p(send_keys.data_ptr()) if send_keys is not None else None,
+                                       p(reply.data_ptr()), cap, p(reply_off.data_ptr()), p(stream_reply.data_ptr()),
+                                       p(msgs.data_ptr()), p(count.data_ptr()), p(info.data_ptr()), ctypes.byref(n),
+                                       self._stream(stream))
+        _check(rc, "wsg_reply_streams")
+        return reply, reply_off, stream_reply, msgs, count, state, info, frame_start, stream_first, n.value
 
     def prepare_decode(self, wire, frame_start, out, info, stream=None):
         """wsg_decode_batch on fixed buffers (a server's batch arena), with

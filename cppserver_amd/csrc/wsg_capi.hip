@@ -1271,18 +1271,16 @@ int wsg_frame_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_
     return scratch_leave(c->frame_order, s, ordered);
 }
 
-int wsg_decode_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_stream_span* d_span,
-                       uint32_t n_streams, wsg_stream_state* d_state, uint64_t* d_frame_start, uint32_t frame_cap,
-                       uint32_t* d_stream_first, uint8_t* d_msg, uint64_t msg_cap, wsg_msg* d_msgs, uint64_t* d_count,
-                       wsg_recv_info* d_info, uint32_t* n_frames_out, void* stream)
+namespace {
+
+// wsg_decode_streams and wsg_reply_streams: the framer, one synchronisation
+// to read the frame count, `messages(n)` over the frames it found, the spans'
+// consumed lowered to the first tail frame.
+extern "C++" template <class Messages>
+int streams_then(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_stream_span* d_span, uint32_t n_streams,
+                 wsg_stream_state* d_state, uint64_t* d_frame_start, uint32_t frame_cap, uint32_t* d_stream_first,
+                 uint64_t* d_count, uint32_t* n_frames_out, void* stream, Messages messages)
 {
-    if (!c || !n_frames_out || !d_count || (n_streams && !d_state) || (msg_cap && !d_msg) ||
-        (frame_cap && (!d_msgs || !d_info)) || !aligned16(d_msg))
-        return WSG_EINVAL;
-    if (c->check && (!in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) || !in_alloc(d_msg, msg_cap) ||
-                     !in_alloc(d_msgs, uint64_t(frame_cap) * sizeof(wsg_msg)) ||
-                     !in_alloc(d_info, uint64_t(frame_cap) * sizeof(wsg_recv_info))))
-        return WSG_EINVAL;
     hipStream_t s = pick(c, stream);
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     WSG_HIP(hipStreamIsCapturing(s, &cap));
@@ -1301,11 +1299,110 @@ int wsg_decode_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg
         return WSG_ENOMEM;
     const uint32_t n = uint32_t(found);
     *n_frames_out = n;
-    if (int rc = wsg_decode_messages(c, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams, d_state, d_msg,
-                                     msg_cap, d_msgs, d_count, d_info, stream))
+    if (int rc = messages(n))
         return rc;
     WSG_HIP(wsg::launch_frame_tail(s, d_span, n_streams, d_frame_start, d_stream_first, d_state, n));
     return WSG_OK;
+}
+
+} // namespace
+
+int wsg_decode_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_stream_span* d_span,
+                       uint32_t n_streams, wsg_stream_state* d_state, uint64_t* d_frame_start, uint32_t frame_cap,
+                       uint32_t* d_stream_first, uint8_t* d_msg, uint64_t msg_cap, wsg_msg* d_msgs, uint64_t* d_count,
+                       wsg_recv_info* d_info, uint32_t* n_frames_out, void* stream)
+{
+    if (!c || !n_frames_out || !d_count || (n_streams && !d_state) || (msg_cap && !d_msg) ||
+        (frame_cap && (!d_msgs || !d_info)) || !aligned16(d_msg))
+        return WSG_EINVAL;
+    if (c->check && (!in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) || !in_alloc(d_msg, msg_cap) ||
+                     !in_alloc(d_msgs, uint64_t(frame_cap) * sizeof(wsg_msg)) ||
+                     !in_alloc(d_info, uint64_t(frame_cap) * sizeof(wsg_recv_info))))
+        return WSG_EINVAL;
+    return streams_then(c, d_wire, wire_len, d_span, n_streams, d_state, d_frame_start, frame_cap, d_stream_first,
+                        d_count, n_frames_out, stream, [&](uint32_t n) {
+                            return wsg_decode_messages(c, d_wire, wire_len, d_frame_start, n, d_stream_first,
+                                                       n_streams, d_state, d_msg, msg_cap, d_msgs, d_count, d_info,
+                                                       stream);
+                        });
+}
+
+// Replies out of a batch of frames: wsg_decode_messages' plan with the reply
+// frames' geometry scanned behind it, then the same gather, its destination
+// the reply wire.
+int wsg_reply_messages(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const uint64_t* d_frame_start, uint32_t n,
+                       const uint32_t* d_stream_first, uint32_t n_streams, wsg_stream_state* d_state,
+                       const uint8_t reply_op[5], int mask, const uint32_t* d_send_key, uint8_t* d_reply,
+                       uint64_t reply_cap, uint64_t* d_reply_off, uint64_t* d_stream_reply, wsg_msg* d_msgs,
+                       uint64_t* d_count, wsg_recv_info* d_info, void* stream)
+{
+    if (!c || !d_count || !d_stream_first || !reply_op || !d_reply_off || !d_stream_reply || (wire_len && !d_wire) ||
+        (reply_cap && !d_reply) || (n && (!d_frame_start || !d_info || !d_msgs || n_streams == 0)) ||
+        (n_streams && !d_state) || n == UINT32_MAX || n_streams == UINT32_MAX)
+        return WSG_EINVAL;
+    if (!aligned16(d_wire) || !aligned16(d_reply))
+        return WSG_EINVAL;
+    if (c->check &&
+        (!in_alloc(d_wire, (wire_len + 15) & ~uint64_t(15)) || !in_alloc(d_frame_start, uint64_t(n) * 8) ||
+         !in_alloc(d_stream_first, (uint64_t(n_streams) + 1) * 4) ||
+         !in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) ||
+         (d_send_key && !in_alloc(d_send_key, uint64_t(n_streams) * 4)) || !in_alloc(d_reply, reply_cap) ||
+         !in_alloc(d_reply_off, (uint64_t(n) + 1) * 8) || !in_alloc(d_stream_reply, (uint64_t(n_streams) + 1) * 8) ||
+         !in_alloc(d_msgs, uint64_t(n) * sizeof(wsg_msg)) || !in_alloc(d_count, 4 * 8) ||
+         !in_alloc(d_info, uint64_t(n) * sizeof(wsg_recv_info))))
+        return WSG_EINVAL;
+    hipStream_t s = pick(c, stream);
+    wsg::ReplyRule rule;
+    for (int k = 0; k < 5; ++k)
+        rule.op[k] = reply_op[k];
+    rule.mask = mask ? 1 : 0;
+    // the pieces of wsg_decode_messages: the same frames, cut at 16-byte
+    // chunks of another destination
+    const uint64_t pieces_cap = wire_len / wsg::PIECE + 2 * uint64_t(n) + 1;
+    if (pieces_cap > UINT32_MAX)
+        return WSG_EINVAL;
+    if (int rc = ensure_array(c->d_msg_plan, c->msg_plan_cap, wsg::msg_plan_layout(nullptr, n, nullptr)))
+        return rc;
+    if (int rc = ensure_array(c->d_msg_pieces, c->msg_pieces_cap, pieces_cap))
+        return rc;
+    wsg::MsgPlan plan;
+    wsg::msg_plan_layout(c->d_msg_plan, n, &plan);
+    bool ordered = false;
+    if (int rc = scratch_enter(c->msg_order, s, &ordered))
+        return rc;
+    WSG_HIP(wsg::launch_reply_plan(s, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams, d_state, rule,
+                                   d_send_key, d_reply, reply_cap, d_reply_off, d_stream_reply, d_msgs, d_count,
+                                   d_info, plan, c->d_msg_pieces, pieces_cap, c->d_err));
+    if (n == 0)
+        return scratch_leave(c->msg_order, s, ordered);
+    const int t = timing_begin(c, s);
+    WSG_HIP(wsg::launch_reply_gather(s, grid_for(c, ceil_div(pieces_cap, wsg::BLOCK / 64), c->enc_blocks_per_cu),
+                                     d_wire, plan, c->d_msg_pieces, pieces_cap, d_reply, reply_cap));
+    timing_end(c, s, t);
+    return scratch_leave(c->msg_order, s, ordered);
+}
+
+int wsg_reply_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_stream_span* d_span,
+                      uint32_t n_streams, wsg_stream_state* d_state, uint64_t* d_frame_start, uint32_t frame_cap,
+                      uint32_t* d_stream_first, const uint8_t reply_op[5], int mask, const uint32_t* d_send_key,
+                      uint8_t* d_reply, uint64_t reply_cap, uint64_t* d_reply_off, uint64_t* d_stream_reply,
+                      wsg_msg* d_msgs, uint64_t* d_count, wsg_recv_info* d_info, uint32_t* n_frames_out, void* stream)
+{
+    if (!c || !n_frames_out || !d_count || !reply_op || !d_reply_off || !d_stream_reply || (n_streams && !d_state) ||
+        (reply_cap && !d_reply) || (frame_cap && (!d_msgs || !d_info)) || !aligned16(d_reply))
+        return WSG_EINVAL;
+    if (c->check &&
+        (!in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) || !in_alloc(d_reply, reply_cap) ||
+         !in_alloc(d_reply_off, (uint64_t(frame_cap) + 1) * 8) ||
+         !in_alloc(d_msgs, uint64_t(frame_cap) * sizeof(wsg_msg)) ||
+         !in_alloc(d_info, uint64_t(frame_cap) * sizeof(wsg_recv_info))))
+        return WSG_EINVAL;
+    return streams_then(c, d_wire, wire_len, d_span, n_streams, d_state, d_frame_start, frame_cap, d_stream_first,
+                        d_count, n_frames_out, stream, [&](uint32_t n) {
+                            return wsg_reply_messages(c, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams,
+                                                      d_state, reply_op, mask, d_send_key, d_reply, reply_cap,
+                                                      d_reply_off, d_stream_reply, d_msgs, d_count, d_info, stream);
+                        });
 }
 
 namespace {

@@ -93,6 +93,12 @@ struct MsgPlan {
     uint32_t* bp_pre;
     uint32_t* bq;
     uint32_t* bq_pre;
+    // wsg_reply_messages only
+    uint64_t* rex;        // n: block-local reply bytes of the FIN frames before frame i
+    uint64_t* brep;       // nb: block sums of reply bytes, then their exclusive prefixes
+    uint64_t* brep_pre;
+    uint64_t* brn;        // nb: block sums of reply frames
+    uint64_t* rtot;       // tot as the gather of a reply reads it: [2] reply bytes, [3] pieces
 };
 // Bytes of that block for n frames; plan (or null) gets the pointers into base.
 uint64_t msg_plan_layout(uint8_t* base, uint32_t n, MsgPlan* plan);
@@ -115,6 +121,26 @@ hipError_t launch_msg_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_len
 // The gather pass: every delivered payload byte, unmasked, to its place in msg.
 hipError_t launch_msg_gather(hipStream_t s, int grid, const uint8_t* wire, const MsgPlan& plan,
                              const MsgPiece* pieces, uint64_t pieces_cap, uint8_t* msg, uint64_t msg_cap);
+
+// ---- replies (wsg_reply_messages) -------------------------------------------
+// The caller's rule, by value in the kernels' arguments.
+struct ReplyRule {
+    uint8_t op[5];   // by WSG_CB_*: the reply's first header byte, 0 (none) or WSG_REPLY_SAME
+    uint8_t mask;
+};
+// The plan pass of a reply: launch_msg_plan's outputs but the d_msg layout's
+// capacity check, and d_reply_off, d_stream_reply, d_count[2..3], every reply
+// frame's header and status prefix, and piece records whose destination is
+// the reply wire; latches frame errors and WSG_ENOMEM (reply_cap).
+hipError_t launch_reply_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
+                             const uint32_t* stream_first, uint32_t n_streams, wsg_stream_state* state,
+                             const ReplyRule& rule, const uint32_t* send_key, uint8_t* reply, uint64_t reply_cap,
+                             uint64_t* reply_off, uint64_t* stream_reply, wsg_msg* msgs, uint64_t* count,
+                             wsg_recv_info* info, const MsgPlan& plan, MsgPiece* pieces, uint64_t pieces_cap,
+                             unsigned long long* err);
+// k_msg_gather over those records: every replied payload byte, re-keyed, to its place in reply.
+hipError_t launch_reply_gather(hipStream_t s, int grid, const uint8_t* wire, const MsgPlan& plan,
+                               const MsgPiece* pieces, uint64_t pieces_cap, uint8_t* reply, uint64_t reply_cap);
 
 // ---- the device framer (wsg_frame_streams) ---------------------------------
 // Scratch of one call, carved out of one device array of uint64 (one block =

@@ -2579,6 +2579,73 @@ __device__ __forceinline__ void fill_pieces_wave(MsgPiece* pieces, uint64_t lo, 
     }
 }
 
+
+// The message that FIN frame i ends (ws.cpp:411-452), as the wsg_msg fields.
+struct MsgRec {
+    uint64_t off, len;
+    uint32_t stream, first, kind, op;
+    int32_t status;
+};
+
+__device__ __forceinline__ MsgRec msg_at_fin(const uint8_t* __restrict__ wire, const wsg_recv_info* __restrict__ info,
+                                             uint32_t n, const uint32_t* __restrict__ sf,
+                                             const wsg_stream_state* __restrict__ state, const MsgPlan& P, uint32_t i,
+                                             uint64_t frame_len)
+{
+    const uint32_t j = P.sidx[i];
+    const uint32_t ff = min(max(last_fin_before(P, n, i), sf[j]), i);   // the message's first frame
+    const uint64_t base = dst_of(P, ff), end = dst_of(P, i) + frame_len;
+    const uint32_t op = sticky_opcode(P, info, state, i, j);
+    uint64_t off = base, len = end - base;
+    uint32_t kind = 0;
+    int32_t status = 0;
+    if (op == WSG_TEXT || op == WSG_BINARY) {
+        kind = WSG_CB_RECEIVED;
+    } else if (op == WSG_PING) {
+        kind = WSG_CB_PING;
+    } else if (op == WSG_PONG) {
+        kind = WSG_CB_PONG;
+    } else if (op == WSG_CLOSE) {
+        kind = WSG_CB_CLOSE;
+        status = 1000;
+        if (len >= 2) {   // ws.cpp:435-439: the buffer's first two bytes, wherever their frames are
+            uint32_t sb[2];
+            for (uint32_t t = 0; t < 2; ++t) {
+                const uint64_t x = base + t;
+                uint32_t a = ff, b = i + 1;   // last k in [ff, i] with dst_of(k) <= x holds byte x
+                while (b - a > 1) {
+                    const uint32_t mid = a + (b - a) / 2;
+                    if (dst_of(P, mid) <= x)
+                        a = mid;
+                    else
+                        b = mid;
+                }
+                const uint64_t o = x - dst_of(P, a);
+                // (o < len unless stream_first is malformed: never a read past the payload)
+                sb[t] = o < info[a].len ? uint32_t(wire[info[a].payload_off + o]) ^ key_byte(info[a].key, o) : 0u;
+            }
+            status = int32_t((sb[0] << 8) | sb[1]);
+            off += 2;
+            len -= 2;
+        }
+    }
+    return MsgRec{off, len, j, ff, kind, op, status};
+}
+
+__device__ __forceinline__ void put_msg(wsg_msg* m, const MsgRec& r, uint32_t last)
+{
+    static_assert(sizeof(wsg_msg) == 40 && offsetof(wsg_msg, stream) == 16 && offsetof(wsg_msg, nframes) == 24 &&
+                      offsetof(wsg_msg, status) == 28 && offsetof(wsg_msg, kind) == 32 &&
+                      offsetof(wsg_msg, opcode) == 33,
+                  "wsg_msg layout");
+    uint64_t* w = reinterpret_cast<uint64_t*>(m);
+    w[0] = r.off;
+    w[1] = r.len;
+    w[2] = uint64_t(r.stream) | (uint64_t(r.first) << 32);
+    w[3] = uint64_t(last - r.first + 1) | (uint64_t(uint32_t(r.status)) << 32);
+    w[4] = uint64_t(r.kind) | (uint64_t(r.op) << 8);
+}
+
 } // namespace
 
 __global__ __launch_bounds__(BLOCK) void k_msg_scan_local(const uint8_t* __restrict__ wire, uint64_t wire_len,
@@ -2714,55 +2781,8 @@ __global__ __launch_bounds__(BLOCK) void k_msg_finalize(const uint8_t* __restric
         plen = r.len;
         key = r.key;
         d0 = dst_of(P, i);
-        if (r.fin) {
-            static_assert(sizeof(wsg_msg) == 40 && offsetof(wsg_msg, stream) == 16 &&
-                              offsetof(wsg_msg, nframes) == 24 && offsetof(wsg_msg, status) == 28 &&
-                              offsetof(wsg_msg, kind) == 32 && offsetof(wsg_msg, opcode) == 33,
-                          "wsg_msg layout");
-            const uint32_t j = P.sidx[i];
-            const uint32_t ff = min(max(last_fin_before(P, n, i), sf[j]), i);   // the message's first frame
-            const uint64_t base = dst_of(P, ff), end = dst_of(P, i) + r.len;
-            const uint32_t op = sticky_opcode(P, info, state, i, j);
-            uint64_t off = base, len = end - base;
-            uint32_t kind = 0;
-            int32_t status = 0;
-            if (op == WSG_TEXT || op == WSG_BINARY) {
-                kind = WSG_CB_RECEIVED;
-            } else if (op == WSG_PING) {
-                kind = WSG_CB_PING;
-            } else if (op == WSG_PONG) {
-                kind = WSG_CB_PONG;
-            } else if (op == WSG_CLOSE) {
-                kind = WSG_CB_CLOSE;
-                status = 1000;
-                if (len >= 2) {   // ws.cpp:435-439: the buffer's first two bytes, wherever their frames are
-                    uint32_t sb[2];
-                    for (uint32_t t = 0; t < 2; ++t) {
-                        const uint64_t x = base + t;
-                        uint32_t a = ff, b = i + 1;   // last k in [ff, i] with dst_of(k) <= x holds byte x
-                        while (b - a > 1) {
-                            const uint32_t mid = a + (b - a) / 2;
-                            if (dst_of(P, mid) <= x)
-                                a = mid;
-                            else
-                                b = mid;
-                        }
-                        const uint64_t o = x - dst_of(P, a);
-                        // (o < len unless stream_first is malformed: never a read past the payload)
-                        sb[t] = o < info[a].len ? uint32_t(wire[info[a].payload_off + o]) ^ key_byte(info[a].key, o) : 0u;
-                    }
-                    status = int32_t((sb[0] << 8) | sb[1]);
-                    off += 2;
-                    len -= 2;
-                }
-            }
-            uint64_t* w = reinterpret_cast<uint64_t*>(msgs + fins_before(P, n, i));
-            w[0] = off;
-            w[1] = len;
-            w[2] = uint64_t(j) | (uint64_t(ff) << 32);
-            w[3] = uint64_t(i - ff + 1) | (uint64_t(uint32_t(status)) << 32);
-            w[4] = uint64_t(kind) | (uint64_t(op) << 8);
-        }
+        if (r.fin)
+            put_msg(msgs + fins_before(P, n, i), msg_at_fin(wire, info, n, sf, state, P, i, r.len), i);
     }
     fill_pieces_wave(pieces, lo, hi, poff, d0, plen, key);
 }
@@ -2786,6 +2806,168 @@ __global__ __launch_bounds__(BLOCK) void k_msg_state(const wsg_recv_info* __rest
         }
     }
     *reinterpret_cast<uint64_t*>(state + j) = uint64_t(consumed) | (uint64_t(op & 0xFFu) << 32);
+}
+
+// ---- replies (wsg_reply_messages) -------------------------------------------
+// The plan above up to k_msg_bytes_blocks, then, one lane per frame again:
+//   k_reply_local     FIN lanes write their wsg_msg and size the reply frame
+//                     (send_geom); block-local sums of the reply sizes.  The
+//                     sum over the FIN frames before frame i is the reply
+//                     offset of the message frame i belongs to, FIN or not.
+//   k_reply_blocks    those over the block partials; d_count[2..3]; the
+//                     capacity latch; the gather's totals (P.rtot)
+//   k_reply_finalize  FIN lanes: d_reply_off, header and status prefix (byte
+//                     stores, frame_head's bytes); every lane: its frame's
+//                     piece records with the reply wire as destination and
+//                     the receive key XOR the send key at the destination's
+//                     phase; a lane per stream: d_stream_reply
+// and k_msg_gather over those records: every payload byte is read once from
+// the received wire and written once, re-keyed, into its reply frame.
+
+namespace {
+
+// What message r is answered with: the first header byte (0: nothing), the
+// data length and the status of the PrepareSendFrame call.
+struct ReplyOf {
+    uint8_t op;
+    uint64_t len;
+    int32_t status;
+};
+
+__device__ __forceinline__ ReplyOf reply_of(const ReplyRule& rule, uint32_t kind, uint32_t opcode, uint64_t len,
+                                            int32_t status)
+{
+    const uint8_t v = kind >= 1 && kind <= 4 ? rule.op[kind] : uint8_t(0);
+    ReplyOf r;
+    r.op = v == WSG_REPLY_SAME ? uint8_t(WSG_FIN | opcode) : v;
+    r.len = kind == WSG_CB_CLOSE ? 0 : len;   // a close reply carries the status and no data
+    r.status = kind == WSG_CB_CLOSE ? status : 0;
+    return r;
+}
+
+__device__ __forceinline__ uint64_t reply_size(const ReplyRule& rule, const ReplyOf& r)
+{
+    if (!r.op)
+        return 0;
+    const SendGeom g = send_geom(r.op, rule.mask != 0, r.len, r.status);
+    return g.hdr + g.body;
+}
+
+// Reply bytes of the FIN frames before frame k, for k in [0, n].
+__device__ __forceinline__ uint64_t reply_before(const MsgPlan& P, uint32_t n, uint32_t k)
+{
+    return k < n ? P.rex[k] + P.brep_pre[k / BLOCK] : P.rtot[2];
+}
+
+} // namespace
+
+__global__ __launch_bounds__(BLOCK) void k_reply_local(const uint8_t* __restrict__ wire,
+                                                       const wsg_recv_info* __restrict__ info, uint32_t n,
+                                                       const uint32_t* __restrict__ sf,
+                                                       const wsg_stream_state* __restrict__ state, MsgPlan P,
+                                                       ReplyRule rule, wsg_msg* __restrict__ msgs)
+{
+    const uint64_t i64 = uint64_t(blockIdx.x) * BLOCK + threadIdx.x;
+    const uint32_t i = uint32_t(i64);
+    uint64_t size = 0;
+    if (i64 < n && info[i].fin) {
+        const MsgRec m = msg_at_fin(wire, info, n, sf, state, P, i, info[i].len);
+        put_msg(msgs + fins_before(P, n, i), m, i);
+        size = reply_size(rule, reply_of(rule, m.kind, m.op, m.len, m.status));
+    }
+    uint64_t tb, tn;
+    const uint64_t eb = block_scan_ex(size, OpAdd{}, &tb);
+    block_scan_ex(uint64_t(size != 0), OpAdd{}, &tn);
+    if (i64 < n)
+        P.rex[i] = eb;
+    if (threadIdx.x == 0) {
+        P.brep[blockIdx.x] = tb;
+        P.brn[blockIdx.x] = tn;
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_reply_blocks(MsgPlan P, uint32_t nb, uint32_t n, uint64_t reply_cap,
+                                                        uint64_t* __restrict__ count, unsigned long long* err)
+{
+    uint64_t cb = 0, cn = 0;
+    for (uint32_t c = 0; c < nb; c += BLOCK) {
+        const uint32_t b = c + threadIdx.x;
+        uint64_t tb, tn;
+        const uint64_t eb = block_scan_ex(b < nb ? P.brep[b] : uint64_t(0), OpAdd{}, &tb);
+        block_scan_ex(b < nb ? P.brn[b] : uint64_t(0), OpAdd{}, &tn);
+        if (b < nb)
+            P.brep_pre[b] = cb + eb;
+        cb += tb;
+        cn += tn;
+    }
+    if (threadIdx.x == 0) {
+        P.rtot[2] = cb;         // k_msg_gather's view of the totals: bytes against the capacity,
+        P.rtot[3] = P.tot[3];   // and the piece count
+        count[2] = cb;
+        count[3] = cn;
+        if (cb > reply_cap)   // behind every frame error: the latch keeps the smallest
+            atomicMin(err, (static_cast<unsigned long long>(n) << 8) | static_cast<unsigned long long>(-WSG_ENOMEM));
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_reply_finalize(const wsg_recv_info* __restrict__ info, uint32_t n,
+                                                          const uint32_t* __restrict__ sf, uint32_t ns, MsgPlan P,
+                                                          ReplyRule rule, const uint32_t* __restrict__ send_key,
+                                                          const wsg_msg* __restrict__ msgs,
+                                                          uint8_t* __restrict__ reply, uint64_t reply_cap,
+                                                          uint64_t* __restrict__ reply_off,
+                                                          uint64_t* __restrict__ stream_reply,
+                                                          MsgPiece* __restrict__ pieces, uint64_t pieces_cap)
+{
+    const uint64_t i64 = uint64_t(blockIdx.x) * BLOCK + threadIdx.x;
+    const uint32_t i = uint32_t(i64);
+    const uint64_t total = P.rtot[2], nmsg = P.tot[0];
+    // connection j's replies start where its first message's does
+    for (uint64_t j = i64; j <= ns; j += uint64_t(gridDim.x) * BLOCK)
+        stream_reply[j] = reply_before(P, n, min(sf[j], n));
+    if (i64 == 0)
+        reply_off[nmsg] = total;
+    uint64_t lo = 0, hi = 0, poff = 0, d0 = 0, plen = 0;
+    uint32_t key = 0;
+    if (i64 < n) {
+        lo = min(pieces_before(P, n, i), pieces_cap);
+        hi = min(pieces_before(P, n, i + 1), pieces_cap);
+        if (hi < lo)
+            hi = lo;
+        const wsg_recv_info r = info[i];
+        const uint64_t m = fins_before(P, n, i);
+        if ((r.fin || hi > lo) && m < nmsg) {   // frame i belongs to message m
+            const uint32_t* w = reinterpret_cast<const uint32_t*>(msgs + m);
+            const uint64_t moff = uint64_t(w[0]) | (uint64_t(w[1]) << 32);
+            const uint64_t mlen = uint64_t(w[2]) | (uint64_t(w[3]) << 32);
+            const uint32_t j = w[4], kind = w[8] & 0xFFu, opcode = (w[8] >> 8) & 0xFFu;
+            const ReplyOf a = reply_of(rule, kind, opcode, mlen, int32_t(w[7]));
+            const uint64_t at = reply_before(P, n, i);
+            const uint32_t skey = send_key ? send_key[j] : 0u;
+            if (r.fin)
+                reply_off[m] = at;
+            if (a.op) {
+                const FrameRec R = make_rec(at, nullptr, a.len, skey, a.status, a.op, rule.mask != 0);
+                if (r.fin && total <= reply_cap) {
+                    const v4u h = frame_head(R);
+                    for (uint32_t t = 0; t < R.hdr + R.prefix; ++t)
+                        reply[at + t] = uint8_t(lane_byte(h, t));
+                }
+                // data byte dst_of(i) - moff of the message: c bytes into the reply's payload
+                // (inside the message unless stream_first is malformed: never a store outside the frame)
+                const uint64_t rel = dst_of(P, i) - moff;
+                if (a.len && dst_of(P, i) >= moff && rel <= a.len && r.len <= a.len - rel) {
+                    const uint64_t c = R.prefix + rel;
+                    poff = r.payload_off;
+                    plen = r.len;
+                    d0 = R.pw + c;
+                    key = r.key ^ key_rot(skey, uint32_t(c));
+                }
+            }
+        }
+    }
+    // (a frame whose message gets no data keeps d0 = plen = 0: its pieces are empty)
+    fill_pieces_wave(pieces, lo, hi, poff, d0, plen, key);
 }
 
 __global__ __launch_bounds__(BLOCK) void k_msg_gather(const uint8_t* __restrict__ wire,
@@ -2930,6 +3112,11 @@ uint64_t msg_plan_layout(uint8_t* base, uint32_t n, MsgPlan* plan)
     P.bp_pre = reinterpret_cast<uint32_t*>(take(nb * 4));
     P.bq = reinterpret_cast<uint32_t*>(take(nb * 4));
     P.bq_pre = reinterpret_cast<uint32_t*>(take(nb * 4));
+    P.rex = reinterpret_cast<uint64_t*>(take(uint64_t(n) * 8));
+    P.brep = reinterpret_cast<uint64_t*>(take(nb * 8));
+    P.brep_pre = reinterpret_cast<uint64_t*>(take(nb * 8));
+    P.brn = reinterpret_cast<uint64_t*>(take(nb * 8));
+    P.rtot = reinterpret_cast<uint64_t*>(take(4 * 8));
     if (plan)
         *plan = P;
     return at;
@@ -2962,6 +3149,49 @@ hipError_t launch_msg_gather(hipStream_t s, int grid, const uint8_t* wire, const
                              const MsgPiece* pieces, uint64_t pieces_cap, uint8_t* msg, uint64_t msg_cap)
 {
     k_msg_gather<<<grid, BLOCK, 0, s>>>(wire, plan.tot, pieces, pieces_cap, msg, msg_cap);
+    return hipGetLastError();
+}
+
+hipError_t launch_reply_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
+                             const uint32_t* stream_first, uint32_t n_streams, wsg_stream_state* state,
+                             const ReplyRule& rule, const uint32_t* send_key, uint8_t* reply, uint64_t reply_cap,
+                             uint64_t* reply_off, uint64_t* stream_reply, wsg_msg* msgs, uint64_t* count,
+                             wsg_recv_info* info, const MsgPlan& plan, MsgPiece* pieces, uint64_t pieces_cap,
+                             unsigned long long* err)
+{
+    const uint32_t nb = uint32_t((uint64_t(n) + BLOCK - 1) / BLOCK);
+    if (n == 0) {   // no frame: no message, no reply, every stream unchanged with nothing consumed
+        if (hipError_t e = hipMemsetAsync(plan.tot, 0, 4 * sizeof(uint64_t), s); e != hipSuccess)
+            return e;
+        if (hipError_t e = hipMemsetAsync(plan.rtot, 0, 4 * sizeof(uint64_t), s); e != hipSuccess)
+            return e;
+        if (hipError_t e = hipMemsetAsync(count, 0, 4 * sizeof(uint64_t), s); e != hipSuccess)
+            return e;
+        if (hipError_t e = hipMemsetAsync(reply_off, 0, sizeof(uint64_t), s); e != hipSuccess)
+            return e;
+        if (hipError_t e = hipMemsetAsync(stream_reply, 0, (uint64_t(n_streams) + 1) * sizeof(uint64_t), s);
+            e != hipSuccess)
+            return e;
+    } else {
+        k_msg_scan_local<<<nb, BLOCK, 0, s>>>(wire, wire_len, fs, n, stream_first, n_streams, info, plan, err);
+        k_msg_scan_blocks<<<1, BLOCK, 0, s>>>(plan, nb, count);
+        k_msg_bytes_local<<<nb, BLOCK, 0, s>>>(info, n, stream_first, plan);
+        // (no d_msg: its size, d_count[1], meets no capacity)
+        k_msg_bytes_blocks<<<1, BLOCK, 0, s>>>(plan, nb, n, UINT64_MAX, count, err);
+        k_reply_local<<<nb, BLOCK, 0, s>>>(wire, info, n, stream_first, state, plan, rule, msgs);
+        k_reply_blocks<<<1, BLOCK, 0, s>>>(plan, nb, n, reply_cap, count, err);
+        k_reply_finalize<<<nb, BLOCK, 0, s>>>(info, n, stream_first, n_streams, plan, rule, send_key, msgs, reply,
+                                              reply_cap, reply_off, stream_reply, pieces, pieces_cap);
+    }
+    if (n_streams)
+        k_msg_state<<<(n_streams + BLOCK - 1) / BLOCK, BLOCK, 0, s>>>(info, n, stream_first, n_streams, state, plan);
+    return hipGetLastError();
+}
+
+hipError_t launch_reply_gather(hipStream_t s, int grid, const uint8_t* wire, const MsgPlan& plan,
+                               const MsgPiece* pieces, uint64_t pieces_cap, uint8_t* reply, uint64_t reply_cap)
+{
+    k_msg_gather<<<grid, BLOCK, 0, s>>>(wire, plan.rtot, pieces, pieces_cap, reply, reply_cap);
     return hipGetLastError();
 }
 

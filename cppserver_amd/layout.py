@@ -74,6 +74,14 @@ WSG_OK, WSG_EINVAL, WSG_ETRUNC, WSG_ENOMEM, WSG_EHIP = 0, -22, -61, -12, -5
 # Callback kinds (include/wsg_capi.h WSG_CB_*).
 CB_RECEIVED, CB_CLOSE, CB_PING, CB_PONG = 1, 2, 3, 4
 
+# wsg_reply_messages' rule: the reply's first header byte by callback kind
+# (0: none; REPLY_SAME: WS_FIN | the message's opcode).  ECHO_REPLY is the
+# reference echo server: onWSReceived -> SendBinaryAsync
+# (performance/ws_echo_server.cpp:23-26), onWSPing -> SendPongAsync
+# (ws_session.h:99-101), nothing sent on a close or a pong.
+REPLY_SAME = 0xFF
+ECHO_REPLY = (0, WS_FIN | WS_BINARY, 0, WS_FIN | WS_PONG, 0)
+
 
 def key_from_bytes(b):
     """_ws_send_mask[0..3] -> the little-endian uint32 the ABI carries."""
@@ -221,3 +229,29 @@ def message_plan(info, stream_first, state=None, payload=None):
         new_state["opcode"][j] = opcode
     table = np.array(msgs, dtype=MSG) if msgs else np.zeros(0, dtype=MSG)
     return table, np.array([len(msgs), used], dtype=np.uint64), new_state
+
+
+def reply_plan(msgs, reply_op, mask, send_keys=None, n_streams=None):
+    """The sizes and offsets of wsg_reply_messages' output (not its bytes).
+
+    ``msgs``: a message_plan table; ``reply_op``: five bytes indexed by CB_*
+    (entry 0 ignored); ``send_keys``: one per stream, or None (keys do not
+    change a size); ``n_streams``: defaults to len(send_keys), else to the
+    last stream of the table + 1.  Returns (reply_off, stream_reply, count):
+    len(msgs) + 1 and n_streams + 1 offsets into the reply wire, and count =
+    [reply bytes, reply frames]."""
+    msgs = np.asarray(msgs, dtype=MSG)
+    if n_streams is None:
+        n_streams = len(send_keys) if send_keys is not None else int(msgs["stream"].max()) + 1 if len(msgs) else 0
+    sizes = np.zeros(len(msgs), dtype=np.uint64)
+    for q, m in enumerate(msgs):
+        kind = int(m["kind"])
+        op = int(reply_op[kind]) if kind else 0
+        op = WS_FIN | int(m["opcode"]) if op == REPLY_SAME else op
+        if op:   # a close reply carries the status and no data
+            sizes[q] = frame_size(op, mask, 0, int(m["status"])) if kind == CB_CLOSE else \
+                frame_size(op, mask, int(m["len"]))
+    reply_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
+    # messages are stream-major: stream j's begin at the first record of a stream >= j
+    stream_reply = reply_off[np.searchsorted(msgs["stream"], np.arange(n_streams + 1))]
+    return reply_off, stream_reply, np.array([int(reply_off[-1]), int((sizes > 0).sum())], dtype=np.uint64)

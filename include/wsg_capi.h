@@ -20,9 +20,10 @@
  *
  * Streams: one thread may drive a ctx on several streams.  wsg_encode_batch
  * calls share one scratch of the ctx (scan partials, piece starts, piece ->
- * frame map), wsg_decode_messages calls another (plan block, piece records)
- * and wsg_frame_streams calls a third (per-stream frame counts, scan
- * partials; wsg_decode_streams is one call of each of the last two);
+ * frame map), wsg_decode_messages and wsg_reply_messages calls another (plan
+ * block, piece records) and wsg_frame_streams calls a third (per-stream frame
+ * counts, scan partials; wsg_decode_streams and wsg_reply_streams are one
+ * call of each of the last two);
  * wsg_decode_batch and the fan-out calls use none.  The calls that
  * share a scratch are ordered across streams on the device, in the order they
  * were made: a call on another stream than the previous one first waits
@@ -31,8 +32,9 @@
  * wsg_encode_batch kernels one after the other.  A call made while its stream
  * is capturing is not ordered: it neither waits nor records, so the caller
  * keeps other users of that scratch off the device while the graph runs.  A
- * graph holding wsg_encode_batch / wsg_decode_messages / wsg_frame_streams
- * launches (wsg_decode_streams synchronises and cannot be captured) names the
+ * graph holding wsg_encode_batch / wsg_decode_messages / wsg_reply_messages /
+ * wsg_frame_streams launches (wsg_decode_streams and wsg_reply_streams
+ * synchronise and cannot be captured) names the
  * scratch addresses it was captured with; a later call that needs a larger
  * scratch frees them (after a device synchronise), and the graph must not be
  * replayed after that: give such a graph a ctx of its own.  Capture no call
@@ -265,6 +267,75 @@ int wsg_decode_streams(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
                        uint64_t* d_frame_start, uint32_t frame_cap, uint32_t* d_stream_first,
                        uint8_t* d_msg, uint64_t msg_cap, wsg_msg* d_msgs, uint64_t* d_count,
                        wsg_recv_info* d_info, uint32_t* n_frames_out, void* stream);
+
+/* ---- replies: received messages to frames to send, on the device ---------- */
+/* (Added without an ABI bump, as wsg_decode_messages was: symbols only.)
+ *
+ * What an echo server does with a batch (performance/ws_echo_server.cpp:
+ * onWSReceived -> SendBinaryAsync, ws_session.h: onWSPing -> SendPongAsync)
+ * in one asynchronous call: the arguments, message rules, d_msgs, d_info,
+ * d_state and frame errors of wsg_decode_messages, but instead of a dense
+ * d_msg the reply frames, ready to send.  Every payload byte is read once
+ * from d_wire and written once into d_reply; d_msgs[m].off / len and
+ * d_count[1] describe the dense layout that wsg_decode_messages would have
+ * produced (no such buffer is written).
+ *
+ * reply_op (host array, read during the call) is indexed by WSG_CB_*; entry
+ * 0 is ignored (a kind-0 message is never answered).  0: no reply to that
+ * kind; WSG_REPLY_SAME: WSG_FIN | the message's opcode; anything else: the
+ * reply's whole first header byte.  The reference echo server is
+ * {0, WSG_FIN|WSG_BINARY, 0, WSG_FIN|WSG_PONG, 0}.
+ *
+ * The reply to message m of stream j is what a session whose _ws_send_mask
+ * is d_send_key[j] (little-endian, as wsg_send_desc.key; NULL: every key 0,
+ * a server) leaves in _ws_send_buffer after PrepareSendFrame(op, mask, data,
+ * size, 0) with the callback's data, or, for a WSG_CB_CLOSE message, after
+ * PrepareSendFrame(op, mask, NULL, 0, msg.status).  Byte-exact with
+ * ws.cpp:212-271 as wsg_encode_batch is: one frame per message however many
+ * fragments it came in, the two-byte prefix on CLOSE/PING/PONG opcodes (a
+ * pong to a non-empty ping carries 00 00 ahead of its data), the XOR with
+ * the send key when mask == 0 too.
+ *
+ * Reply frames lie back to back in d_reply (16-byte aligned, reply_cap
+ * bytes, not overlapping d_wire; wire_len + 14 * n always suffices) in
+ * message order:
+ *   d_reply_off[0..d_count[0]]   (room for n + 1) message m's frame is
+ *                                d_reply[d_reply_off[m], d_reply_off[m+1]),
+ *                                empty when it gets no reply
+ *   d_stream_reply[0..n_streams] connection j's replies are the one range
+ *                                d_reply[d_stream_reply[j], d_stream_reply[j+1])
+ *   d_count[0..4)                messages, bytes of the dense layout, reply
+ *                                bytes, reply frames
+ * When the replies need more than reply_cap bytes no byte of d_reply is
+ * written and wsg_sync reports WSG_ENOMEM (behind every frame error);
+ * everything else is final.
+ * Streams: the call uses the scratch of wsg_decode_messages and is ordered
+ * with those calls across streams (see "Streams" above); the same capture
+ * rule holds: run it once with the same n first.                            */
+#define WSG_REPLY_SAME 0xFF   /* reply opcode byte: WSG_FIN | the message's opcode */
+
+int wsg_reply_messages(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
+                       const uint64_t* d_frame_start, uint32_t n,
+                       const uint32_t* d_stream_first, uint32_t n_streams,
+                       wsg_stream_state* d_state,
+                       const uint8_t reply_op[5], int mask, const uint32_t* d_send_key,
+                       uint8_t* d_reply, uint64_t reply_cap,
+                       uint64_t* d_reply_off, uint64_t* d_stream_reply,
+                       wsg_msg* d_msgs, uint64_t* d_count,
+                       wsg_recv_info* d_info, void* stream);
+
+/* Raw bytes to reply frames: wsg_decode_streams with wsg_reply_messages in
+ * the place of wsg_decode_messages (the framer, one synchronisation of
+ * `stream`, the replies, d_span[j].consumed lowered to the first tail
+ * frame); the same returns.  An echo server's loop is this call, then one
+ * send per d_stream_reply range.                                            */
+int wsg_reply_streams(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
+                      wsg_stream_span* d_span, uint32_t n_streams, wsg_stream_state* d_state,
+                      uint64_t* d_frame_start, uint32_t frame_cap, uint32_t* d_stream_first,
+                      const uint8_t reply_op[5], int mask, const uint32_t* d_send_key,
+                      uint8_t* d_reply, uint64_t reply_cap, uint64_t* d_reply_off, uint64_t* d_stream_reply,
+                      wsg_msg* d_msgs, uint64_t* d_count, wsg_recv_info* d_info,
+                      uint32_t* n_frames_out, void* stream);
 
 /* ---- batch encode: header pack + mask (PrepareSendFrame over many frames) */
 /* Frames are written back to back into d_wire (16-byte aligned, capacity

@@ -1,6 +1,6 @@
 """Register/occupancy report for k_decode and source variants with paths cut
 out (which path sets the kernel's VGPR count), and for k_msg_gather
-(wsg_decode_messages).  Compiles for gfx950 only (no GPU needed).
+(wsg_decode_messages; wsg_reply_messages runs it too) and the reply plan.  Compiles for gfx950 only (no GPU needed).
 
 usage: python tools/regs.py
 """
@@ -48,5 +48,9 @@ if __name__ == "__main__":
     report(cut(src, boundary), "no-boundary")
     report(cut(cut(src, staged), boundary), "no-staged-no-boundary")
     report(src, "k_msg_gather", kernel="_ZN3wsg12k_msg_gather")
+    report(src, "k_msg_finalize", kernel="_ZN3wsg14k_msg_finalize")
+    report(src, "k_reply_local", kernel="_ZN3wsg13k_reply_local")
+    report(src, "k_reply_blocks", kernel="_ZN3wsg14k_reply_blocks")
+    report(src, "k_reply_finalize", kernel="_ZN3wsg16k_reply_finalize")
     report(src, "k_frame_count", kernel="_ZN3wsg13k_frame_count")
     report(src, "k_frame_write", kernel="_ZN3wsg13k_frame_write")
