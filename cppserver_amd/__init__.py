@@ -16,7 +16,8 @@ import numpy as np
 from .layout import (  # noqa: F401  (re-exported)
     CB_CLOSE, CB_PING, CB_PONG, CB_RECEIVED, ECHO_REPLY, MSG, RECV_INFO, REPLY_SAME, SEND_DESC, STREAM_SPAN,
     STREAM_STATE, WS_BINARY, WS_CLOSE, WS_FIN, WS_PING, WS_PONG, WS_TEXT, WSG_EHIP, WSG_EINVAL, WSG_ENOMEM, WSG_ETRUNC,
-    WSG_OK, frame_plan, frame_size, frame_sizes, key_from_bytes, message_plan, reply_plan,
+    WSG_OK, UTF8_CLOSE, UTF8_EVERY, UTF8_TEXT, frame_plan, frame_size, frame_sizes, key_from_bytes, message_plan,
+    reply_plan, utf8_plan,
 )
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -68,6 +69,8 @@ def lib(path=None):
         "wsg_reply_messages": (ci, [vp, vp, u64, vp, u32, vp, u32, vp, vp, ci, vp, vp, u64, vp, vp, vp, vp, vp, vp]),
         "wsg_reply_streams": (ci, [vp, vp, u64, vp, u32, vp, vp, u32, vp, vp, ci, vp, vp, u64, vp, vp, vp, vp, vp,
                                    ctypes.POINTER(u32), vp]),
+        "wsg_check_utf8": (ci, [vp, vp, u64, vp, vp, u32, u32, vp, vp, vp]),
+        "wsg_utf8_valid_up_to": (u64, [vp, u64]),
         "wsg_encode_batch": (ci, [vp, vp, vp, u32, vp, u64, vp, vp]),
         "wsg_fanout_encode": (ci, [vp, vp, u64, vp, u32, ctypes.c_uint8, ci, vp, u64, vp]),
         "wsg_fanout_encode_many": (ci, [vp, vp, vp, vp, vp, u32, vp, u32, ci, vp, u64, vp, vp]),
@@ -154,6 +157,13 @@ def header_unpack(data):
     info = np.zeros(1, dtype=RECV_INFO)
     rc = lib().wsg_header_unpack(data, len(data), _np_ptr(info))
     return rc, info[0]
+
+
+def utf8_valid_up_to(data):
+    """wsg_utf8_valid_up_to: the length of the longest well-formed UTF-8
+    prefix of ``data`` (the host helper built from the rule the kernel runs)."""
+    data = bytes(data)
+    return int(lib().wsg_utf8_valid_up_to(data, len(data)))
 
 
 class _Pinned:
@@ -286,6 +296,41 @@ class Codec:
                                          ctypes.c_void_p(info.data_ptr()), self._stream(stream))
         _check(rc, "wsg_decode_messages")
         return msg, msgs, count, state, info
+
+    # -- UTF-8 of text messages and close reasons -----------------------------
+    def check_utf8(self, msg, msgs, count, which=UTF8_TEXT | UTF8_CLOSE, msg_cap=None, msg_room=None, valid=None,
+                   result=None, stream=None):
+        """wsg_check_utf8 over what decode_messages / decode_streams returned:
+        ``msg`` the message bytes, ``msgs`` the MSG table bytes, ``count``
+        int64[2] (read on the device: no synchronisation needed after the
+        decode on the same stream).  ``which``: UTF8_* bits.  ``msg_cap``
+        defaults to msg's length and ``msg_room`` to the records msgs has room
+        for.  Returns (valid, result): int64[msg_room], valid[m] = the length
+        of message m's longest well-formed prefix (its len when it is valid or
+        not checked), written for m < min(count[0], msg_room); and int64[4] =
+        [invalid messages, the lowest of them or -1, messages checked, bytes
+        checked]."""
+        t = self._torch
+        dev = msg.device
+        if msg_cap is None:
+            msg_cap = int(msg.numel())
+        if msg_room is None:
+            msg_room = int(msgs.numel()) // MSG.itemsize if valid is None else int(valid.numel())
+        cap, room = int(msg_cap), int(msg_room)
+        if valid is None:
+            valid = t.empty(max(room, 1), dtype=t.int64, device=dev)
+        if result is None:
+            result = t.empty(4, dtype=t.int64, device=dev)
+        if (cap > int(msg.numel()) or int(msgs.numel()) < room * MSG.itemsize or int(valid.numel()) < room
+                or valid.element_size() != 8 or int(count.numel()) < 2 or count.element_size() != 8
+                or int(result.numel()) < 4 or result.element_size() != 8):
+            raise WSGError(WSG_EINVAL, "check_utf8: a buffer is smaller than the batch needs")
+        rc = self._L.wsg_check_utf8(self._ctx, ctypes.c_void_p(msg.data_ptr()), cap, ctypes.c_void_p(msgs.data_ptr()),
+                                    ctypes.c_void_p(count.data_ptr()), room, int(which),
+                                    ctypes.c_void_p(valid.data_ptr()), ctypes.c_void_p(result.data_ptr()),
+                                    self._stream(stream))
+        _check(rc, "wsg_check_utf8")
+        return valid, result
 
     # -- the device framer (raw stream bytes -> frame table -> messages) ------
     def _frame_args(self, what, wire, spans, frame_start, frame_cap, stream_first):

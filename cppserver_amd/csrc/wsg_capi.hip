@@ -4,6 +4,7 @@
 // every entry point is produced by a gfx950 kernel.
 #include "wsg_internal.h"
 #include "wsg_env.h"
+#include "wsg_utf8.h"
 #include "wsg_trace.h"
 
 #include <algorithm>
@@ -61,6 +62,7 @@ struct wsg_ctx {
     uint64_t host_direct_max = 4 << 20;   // 1-4 MB batches 1.6-2x faster direct, 16 MB even (profiles/r3/host_direct_sizes.log)
     bool check = false;            // $WSG_CHECK=1: operand ranges validated before every device launch (debug)
     int dec_blocks_per_cu = 4096;  // k_decode grid cap: one 16 KiB tile per block up to 16 GiB of wire (tools/tune.py, round 2: C2 84.3 vs 85.1 us at 48 blocks/CU, 88.1 at two tiles per block; C3 ragged 0.685 vs 0.705 ms at 256, 0.783 at 48)
+    int utf8_blocks_per_cu = 32;   // k_utf8_scan grid cap (a block takes 4 KiB per pass); $WSG_UTF8_BLOCKS_PER_CU
     int fan_waves_per_cu = 6;    // fan-out period path: waves per CU (tools/c4_ab.py, graph-replayed C4: 6 -> 8.10 us, 4 -> 8.16, 8 -> 8.32)
     // fan-out period path: waves per workgroup (A/B $WSG_FAN_WPB; one-wave
     // workgroups measured best: C4 8.5 us against 9.3 at 4 and 9.0 at 8-16,
@@ -961,6 +963,7 @@ struct Knobs {
     bool multi_share = false;                      // $WSG_HOST_MULTI_SHARE=1: multi-context splits keep contexts of one device
     uint64_t enc_launch_pieces = 0;                // $WSG_ENC_LAUNCH_PIECES: pieces per k_encode_mask launch
     int dec_blocks_per_cu = 0;                     // $WSG_DEC_BLOCKS_PER_CU: k_decode grid cap (0: default)
+    int utf8_blocks_per_cu = 0;                    // $WSG_UTF8_BLOCKS_PER_CU: k_utf8_scan grid cap (0: default)
 };
 
 Knobs read_knobs()
@@ -991,6 +994,11 @@ Knobs read_knobs()
         const int v = std::atoi(e);
         if (v >= 1 && v <= 4096)
             k.dec_blocks_per_cu = v;
+    }
+    if (const char* e = wsg::envp("WSG_UTF8_BLOCKS_PER_CU")) {  // (tests: several passes per k_utf8_scan block)
+        const int v = std::atoi(e);
+        if (v >= 1 && v <= 4096)
+            k.utf8_blocks_per_cu = v;
     }
     if (const char* e = wsg::envp("WSG_HOST_MULTI_SHARE"))      // (one-GPU tests of the multi-device split)
         k.multi_share = *e == '1';
@@ -1048,6 +1056,8 @@ int wsg_create(int device, wsg_ctx** out)
     c->enc_launch_pieces = k.enc_launch_pieces;
     if (k.dec_blocks_per_cu)
         c->dec_blocks_per_cu = k.dec_blocks_per_cu;
+    if (k.utf8_blocks_per_cu)
+        c->utf8_blocks_per_cu = k.utf8_blocks_per_cu;
     c->multi_share = k.multi_share;
     *out = c;
     return WSG_OK;
@@ -1234,6 +1244,35 @@ int wsg_decode_messages(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, co
                                    plan, c->d_msg_pieces, pieces_cap, d_msg, msg_cap));
     timing_end(c, s, t);
     return scratch_leave(c->msg_order, s, ordered);
+}
+
+// UTF-8 over the messages of a decode: one lane per record before and behind
+// the payload kernel, which reads every byte of d_msg below the bound once.
+int wsg_check_utf8(wsg_ctx* c, const uint8_t* d_msg, uint64_t msg_cap, const wsg_msg* d_msgs, const uint64_t* d_count,
+                   uint32_t msg_room, uint32_t which, uint64_t* d_valid, uint64_t* d_result, void* stream)
+{
+    if (!c || !d_count || !d_result || (msg_cap && !d_msg) || (msg_room && (!d_msgs || !d_valid)))
+        return WSG_EINVAL;
+    if (!aligned16(d_msg) || (reinterpret_cast<uintptr_t>(d_msgs) & 7u) || (reinterpret_cast<uintptr_t>(d_count) & 7u) ||
+        (reinterpret_cast<uintptr_t>(d_valid) & 7u) || (reinterpret_cast<uintptr_t>(d_result) & 7u))
+        return WSG_EINVAL;
+    if (c->check && (!in_alloc(d_msg, msg_cap) || !in_alloc(d_msgs, uint64_t(msg_room) * sizeof(wsg_msg)) ||
+                     !in_alloc(d_valid, uint64_t(msg_room) * 8) || !in_alloc(d_count, 2 * 8) ||
+                     !in_alloc(d_result, 4 * 8)))
+        return WSG_EINVAL;
+    hipStream_t s = pick(c, stream);
+    const int rec_grid = grid_for(c, ceil_div(msg_room, wsg::BLOCK));   // (at least one block: it seeds d_result)
+    WSG_HIP(wsg::launch_utf8_init(s, rec_grid, d_msgs, d_count, msg_room, d_valid, d_result));
+    if (msg_room == 0)
+        return WSG_OK;
+    if (which && msg_cap) {
+        const int t = timing_begin(c, s);
+        WSG_HIP(wsg::launch_utf8_scan(s, grid_for(c, ceil_div(msg_cap, uint64_t(wsg::BLOCK) * wsg::CHUNK), c->utf8_blocks_per_cu),
+                                      d_msg, msg_cap, d_msgs, d_count, msg_room, which, d_valid));
+        timing_end(c, s, t);
+    }
+    WSG_HIP(wsg::launch_utf8_count(s, rec_grid, d_msgs, d_count, msg_room, msg_cap, which, d_valid, d_result));
+    return WSG_OK;
 }
 
 // The device framer: two walks over every stream (one wave each) with a scan
@@ -2428,6 +2467,11 @@ uint64_t wsg_frame_size(uint8_t opcode, int mask, uint64_t len, int32_t status)
 {
     const wsg::SendGeom g = wsg::send_geom(opcode, mask != 0, len, status);
     return g.hdr + g.body;
+}
+
+uint64_t wsg_utf8_valid_up_to(const uint8_t* buf, uint64_t len)
+{
+    return buf ? wsg::utf8_valid_up_to(buf, len) : 0;
 }
 
 int wsg_header_pack(uint8_t opcode, int mask, uint64_t len, int32_t status, uint32_t key, uint8_t* out)

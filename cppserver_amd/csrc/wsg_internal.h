@@ -167,6 +167,21 @@ hipError_t launch_frame_streams(hipStream_t s, int grid, const uint8_t* wire, ui
 hipError_t launch_frame_tail(hipStream_t s, wsg_stream_span* span, uint32_t ns, const uint64_t* frame_start,
                              const uint32_t* stream_first, const wsg_stream_state* state, uint32_t n);
 
+// ---- UTF-8 on the device (wsg_check_utf8) -----------------------------------
+// k_utf8_init: d_valid[m] = len for m < min(d_count[0], msg_room), and
+// d_result = {0, UINT64_MAX, 0, 0} (grid >= 1 also when msg_room == 0).
+hipError_t launch_utf8_init(hipStream_t s, int grid, const wsg_msg* msgs, const uint64_t* count, uint32_t msg_room,
+                            uint64_t* valid, uint64_t* result);
+// The payload kernel: every 16-byte chunk of d_msg below min(msg_cap,
+// d_count[1]) once, grid-stride (a block takes BLOCK chunks, 4 KiB, per pass);
+// the lowest bad position of a checked message into d_valid by atomicMin.
+hipError_t launch_utf8_scan(hipStream_t s, int grid, const uint8_t* msg, uint64_t msg_cap, const wsg_msg* msgs,
+                            const uint64_t* count, uint32_t msg_room, uint32_t which, uint64_t* valid);
+// d_result: the records with d_valid[m] < len, the lowest of them, the
+// records checked and their bytes.
+hipError_t launch_utf8_count(hipStream_t s, int grid, const wsg_msg* msgs, const uint64_t* count, uint32_t msg_room,
+                             uint64_t msg_cap, uint32_t which, const uint64_t* valid, uint64_t* result);
+
 // Messages of one fan-out launch (blockIdx.y): payload and output offsets.
 constexpr int FAN_MSGS = 32;
 struct FanMsgs {

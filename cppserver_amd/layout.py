@@ -255,3 +255,77 @@ def reply_plan(msgs, reply_op, mask, send_keys=None, n_streams=None):
     # messages are stream-major: stream j's begin at the first record of a stream >= j
     stream_reply = reply_off[np.searchsorted(msgs["stream"], np.arange(n_streams + 1))]
     return reply_off, stream_reply, np.array([int(reply_off[-1]), int((sizes > 0).sum())], dtype=np.uint64)
+
+
+# wsg_check_utf8's `which` bits (include/wsg_capi.h WSG_UTF8_*).
+UTF8_TEXT, UTF8_CLOSE, UTF8_EVERY = 1, 2, 4
+
+
+def _utf8_len(b):
+    """Length a non-continuation byte declares (0: never valid)."""
+    return 1 if b < 0x80 else 0 if b < 0xC2 else 2 if b < 0xE0 else 3 if b < 0xF0 else 4 if b < 0xF5 else 0
+
+
+def _utf8_bad_at(b, i):
+    """The position-local rule of csrc/wsg_utf8.h: is position i of the byte
+    string b bad?  Every byte outside b counts as 00."""
+    def at(j):
+        return b[j] if 0 <= j < len(b) else 0
+
+    def cont(x):
+        return x & 0xC0 == 0x80
+
+    if cont(b[i]):
+        for k in (1, 2, 3):
+            if not cont(at(i - k)):
+                return _utf8_len(at(i - k)) <= k
+        return True
+    size = _utf8_len(b[i])
+    if size <= 1:
+        return size == 0
+    lead, second = b[i], at(i + 1)
+    lo = 0xA0 if lead == 0xE0 else 0x90 if lead == 0xF0 else 0x80
+    hi = 0x9F if lead == 0xED else 0x8F if lead == 0xF4 else 0xBF
+    if not lo <= second <= hi:
+        return True
+    return any(not cont(at(i + k)) for k in range(2, size))
+
+
+def utf8_valid_up_to(data):
+    """Length of the longest well-formed UTF-8 prefix of ``data`` (RFC 3629):
+    the smallest bad position, by the position-local rule (no decoder)."""
+    b = bytes(data)
+    for i in range(len(b)):
+        if b[i] >= 0x80 and _utf8_bad_at(b, i):
+            return i
+    return len(b)
+
+
+def utf8_plan(msgs, msg_bytes, which, msg_cap=None):
+    """wsg_check_utf8 restated on the host over a MSG table and the dense
+    message bytes it describes (``msg_bytes`` is d_msg[0, d_count[1])).
+
+    Returns (valid, result): valid[m] = valid_up_to of message m's data when
+    it is selected by ``which`` (UTF8_* bits, from kind and opcode alone) and
+    lies inside min(msg_cap, len(msg_bytes)), its len otherwise; result =
+    [checked messages that are invalid, the lowest of them or 2**64 - 1,
+    messages checked, bytes checked]."""
+    msgs = np.asarray(msgs, dtype=MSG)
+    buf = np.asarray(msg_bytes, dtype=np.uint8).tobytes()
+    bound = len(buf) if msg_cap is None else min(int(msg_cap), len(buf))
+    valid = np.zeros(len(msgs), dtype=np.uint64)
+    invalid, lowest, checked, nbytes = 0, U64_MAX, 0, 0
+    for m, r in enumerate(msgs):
+        off, size, kind, opcode = int(r["off"]), int(r["len"]), int(r["kind"]), int(r["opcode"])
+        valid[m] = size
+        selected = bool(which & UTF8_EVERY) or (bool(which & UTF8_TEXT) and kind == CB_RECEIVED and opcode == WS_TEXT) \
+            or (bool(which & UTF8_CLOSE) and kind == CB_CLOSE)
+        if not selected or off + size > bound:
+            continue
+        checked += 1
+        nbytes += size
+        valid[m] = utf8_valid_up_to(buf[off: off + size])
+        if int(valid[m]) < size:
+            invalid += 1
+            lowest = min(lowest, m)
+    return valid, np.array([invalid, lowest, checked, nbytes], dtype=np.uint64)

@@ -24,7 +24,7 @@
  * block, piece records) and wsg_frame_streams calls a third (per-stream frame
  * counts, scan partials; wsg_decode_streams and wsg_reply_streams are one
  * call of each of the last two);
- * wsg_decode_batch and the fan-out calls use none.  The calls that
+ * wsg_decode_batch, wsg_check_utf8 and the fan-out calls use none.  The calls that
  * share a scratch are ordered across streams on the device, in the order they
  * were made: a call on another stream than the previous one first waits
  * (hipStreamWaitEvent, no host synchronisation) for an event recorded behind
@@ -336,6 +336,57 @@ int wsg_reply_streams(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
                       uint8_t* d_reply, uint64_t reply_cap, uint64_t* d_reply_off, uint64_t* d_stream_reply,
                       wsg_msg* d_msgs, uint64_t* d_count, wsg_recv_info* d_info,
                       uint32_t* n_frames_out, void* stream);
+
+/* ---- UTF-8: text messages and close reasons checked on the device --------- */
+/* (Added without an ABI bump, as wsg_decode_messages was: symbols and
+ * constants only.)
+ *
+ * RFC 6455 5.6 / 8.1 require a text message, taken over all its fragments,
+ * to be valid UTF-8, and 7.1.6 the same of a close frame's reason; the
+ * endpoint fails the connection with status 1007 otherwise.  The reference
+ * does not validate (it hands the bytes to onWSReceived as they are), so this
+ * is a call of its own behind wsg_decode_messages / wsg_decode_streams, whose
+ * d_msg holds every message unmasked with its fragments joined.
+ *
+ * valid_up_to(b) of a byte string is the length of its longest prefix that is
+ * well-formed UTF-8 (RFC 3629: shortest form only, no surrogates
+ * U+D800-DFFF, nothing above U+10FFFF, the bytes C0, C1 and F5-FF never
+ * valid, a sequence cut off by the end of b invalid): len(b) when b is valid.
+ *
+ * Inputs.  d_msg (16-byte aligned, msg_cap bytes), d_msgs and d_count as the
+ * decode left them on the device: d_count[0] the message count, d_count[1]
+ * the bytes used, both read on the device, so the two calls need no
+ * synchronisation between them on one stream.  M = min(d_count[0], msg_room)
+ * records are looked at; d_valid has room for msg_room words.
+ * What is checked.  Message m < M is selected by `which` (the WSG_UTF8_* bits
+ * or'ed), from its record's kind and opcode alone (a fragmented message whose
+ * sticky opcode at its FIN frame is WSG_TEXT counts as text).  A selected
+ * message is checked when off + len <= min(msg_cap, d_count[1]) (compared
+ * without forming a sum that could wrap); no byte of d_msg at or past that
+ * bound is ever read.  A decode that latched WSG_ENOMEM wrote no byte of
+ * d_msg and left d_count[1] > msg_cap: the caller sees that status at its
+ * wsg_sync and drops the verdicts of that batch.
+ * Outputs.  d_valid[m] for m < M: valid_up_to of d_msg[off, off + len) when
+ * message m is checked, len otherwise; entries at M and beyond are not
+ * written.  d_result[0..4): the checked messages with d_valid[m] < len, the
+ * lowest such m (UINT64_MAX when there is none), the messages checked, the
+ * bytes checked (the sum of their len).  Minima and counts: deterministic.
+ * Asynchronous on `stream`.  Latches nothing: invalid UTF-8 is a result, not
+ * an error of the call, and wsg_sync is unaffected.  Uses no scratch of the
+ * context: it is ordered against nothing (see "Streams" above) and can be
+ * captured without a first plain run.  msg_room == 0, which == 0 and
+ * d_count[0] == 0 are valid.  WSG_EINVAL for a NULL or misaligned operand.  */
+#define WSG_UTF8_TEXT   1u  /* kind == WSG_CB_RECEIVED && opcode == WSG_TEXT            */
+#define WSG_UTF8_CLOSE  2u  /* kind == WSG_CB_CLOSE: the reason, d_msg[off, off + len)  */
+#define WSG_UTF8_EVERY  4u  /* every record, whatever its kind and opcode               */
+
+int wsg_check_utf8(wsg_ctx* ctx, const uint8_t* d_msg, uint64_t msg_cap,
+                   const wsg_msg* d_msgs, const uint64_t* d_count, uint32_t msg_room,
+                   uint32_t which, uint64_t* d_valid, uint64_t* d_result, void* stream);
+
+/* Length of the longest well-formed UTF-8 prefix of buf[0..len) (RFC 3629);
+ * len when the whole buffer is valid.  Host; the rule the kernel runs. */
+uint64_t wsg_utf8_valid_up_to(const uint8_t* buf, uint64_t len);
 
 /* ---- batch encode: header pack + mask (PrepareSendFrame over many frames) */
 /* Frames are written back to back into d_wire (16-byte aligned, capacity

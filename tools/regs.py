@@ -54,3 +54,6 @@ if __name__ == "__main__":
     report(src, "k_reply_finalize", kernel="_ZN3wsg16k_reply_finalize")
     report(src, "k_frame_count", kernel="_ZN3wsg13k_frame_count")
     report(src, "k_frame_write", kernel="_ZN3wsg13k_frame_write")
+    report(src, "k_utf8_init", kernel="_ZN3wsg11k_utf8_init")
+    report(src, "k_utf8_scan", kernel="_ZN3wsg11k_utf8_scan")
+    report(src, "k_utf8_count", kernel="_ZN3wsg12k_utf8_count")
