@@ -170,6 +170,7 @@ namespace {
 constexpr unsigned long long kNoError = ~0ull;
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 // NULL selects HIP's default (null) stream, as in every HIP API.
 inline hipStream_t pick(wsg_ctx*, void* s) { return static_cast<hipStream_t>(s); }
 inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
@@ -1181,6 +1182,30 @@ int decode_launch(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const ui
     return WSG_OK;
 }
 
+// upper bound of the pieces: sum of ceil((size + 15) / PIECE) over frames
+inline uint64_t pieces_bound(uint32_t n, uint64_t wire_cap) { return wire_cap / wsg::PIECE + 2 * uint64_t(n) + 1; }
+
+// The scratch of wsg_decode_messages / wsg_reply_messages for n frames of a
+// wire of wire_len bytes: the plan block and the piece records.  Pieces: at
+// most len / PIECE + 2 per delivered frame, and the delivered payloads of a
+// well-formed batch are disjoint ranges of the wire (the kernels clamp to
+// this bound whatever the batch holds); a reply cuts the same frames at
+// 16-byte chunks of another destination.  Both are the context's: entered
+// behind the previous call's kernels, whatever stream they ran on.
+int msg_scratch(wsg_ctx* c, hipStream_t s, uint32_t n, uint64_t wire_len, wsg::MsgPlan* plan, uint64_t* pieces_cap,
+                bool* ordered)
+{
+    *pieces_cap = pieces_bound(n, wire_len);
+    if (*pieces_cap > UINT32_MAX)
+        return WSG_EINVAL;
+    if (int rc = ensure_array(c->d_msg_plan, c->msg_plan_cap, wsg::msg_plan_layout(nullptr, n, nullptr)))
+        return rc;
+    if (int rc = ensure_array(c->d_msg_pieces, c->msg_pieces_cap, *pieces_cap))
+        return rc;
+    wsg::msg_plan_layout(c->d_msg_plan, n, plan);
+    return scratch_enter(c->msg_order, s, ordered);
+}
+
 } // namespace
 
 int wsg_decode_batch(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const uint64_t* d_frame_start, uint32_t n,
@@ -1218,22 +1243,10 @@ int wsg_decode_messages(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, co
          !in_alloc(d_info, uint64_t(n) * sizeof(wsg_recv_info))))
         return WSG_EINVAL;
     hipStream_t s = pick(c, stream);
-    // pieces: at most len / PIECE + 2 per delivered frame, and the delivered
-    // payloads of a well-formed batch are disjoint ranges of the wire (the
-    // kernels clamp to this bound whatever the batch holds)
-    const uint64_t pieces_cap = wire_len / wsg::PIECE + 2 * uint64_t(n) + 1;
-    if (pieces_cap > UINT32_MAX)
-        return WSG_EINVAL;
-    if (int rc = ensure_array(c->d_msg_plan, c->msg_plan_cap, wsg::msg_plan_layout(nullptr, n, nullptr)))
-        return rc;
-    if (int rc = ensure_array(c->d_msg_pieces, c->msg_pieces_cap, pieces_cap))
-        return rc;
     wsg::MsgPlan plan;
-    wsg::msg_plan_layout(c->d_msg_plan, n, &plan);
-    // the plan block and the piece records are the context's: behind the
-    // previous call's kernels, whatever stream they ran on
+    uint64_t pieces_cap;
     bool ordered = false;
-    if (int rc = scratch_enter(c->msg_order, s, &ordered))
+    if (int rc = msg_scratch(c, s, n, wire_len, &plan, &pieces_cap, &ordered))
         return rc;
     WSG_HIP(wsg::launch_msg_plan(s, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams, d_state, msg_cap,
                                  d_msgs, d_count, d_info, plan, c->d_msg_pieces, pieces_cap, c->d_err));
@@ -1253,8 +1266,7 @@ int wsg_check_utf8(wsg_ctx* c, const uint8_t* d_msg, uint64_t msg_cap, const wsg
 {
     if (!c || !d_count || !d_result || (msg_cap && !d_msg) || (msg_room && (!d_msgs || !d_valid)))
         return WSG_EINVAL;
-    if (!aligned16(d_msg) || (reinterpret_cast<uintptr_t>(d_msgs) & 7u) || (reinterpret_cast<uintptr_t>(d_count) & 7u) ||
-        (reinterpret_cast<uintptr_t>(d_valid) & 7u) || (reinterpret_cast<uintptr_t>(d_result) & 7u))
+    if (!aligned16(d_msg) || !aligned8(d_msgs) || !aligned8(d_count) || !aligned8(d_valid) || !aligned8(d_result))
         return WSG_EINVAL;
     if (c->check && (!in_alloc(d_msg, msg_cap) || !in_alloc(d_msgs, uint64_t(msg_room) * sizeof(wsg_msg)) ||
                      !in_alloc(d_valid, uint64_t(msg_room) * 8) || !in_alloc(d_count, 2 * 8) ||
@@ -1395,19 +1407,10 @@ int wsg_reply_messages(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, con
     for (int k = 0; k < 5; ++k)
         rule.op[k] = reply_op[k];
     rule.mask = mask ? 1 : 0;
-    // the pieces of wsg_decode_messages: the same frames, cut at 16-byte
-    // chunks of another destination
-    const uint64_t pieces_cap = wire_len / wsg::PIECE + 2 * uint64_t(n) + 1;
-    if (pieces_cap > UINT32_MAX)
-        return WSG_EINVAL;
-    if (int rc = ensure_array(c->d_msg_plan, c->msg_plan_cap, wsg::msg_plan_layout(nullptr, n, nullptr)))
-        return rc;
-    if (int rc = ensure_array(c->d_msg_pieces, c->msg_pieces_cap, pieces_cap))
-        return rc;
     wsg::MsgPlan plan;
-    wsg::msg_plan_layout(c->d_msg_plan, n, &plan);
+    uint64_t pieces_cap;
     bool ordered = false;
-    if (int rc = scratch_enter(c->msg_order, s, &ordered))
+    if (int rc = msg_scratch(c, s, n, wire_len, &plan, &pieces_cap, &ordered))
         return rc;
     WSG_HIP(wsg::launch_reply_plan(s, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams, d_state, rule,
                                    d_send_key, d_reply, reply_cap, d_reply_off, d_stream_reply, d_msgs, d_count,
@@ -1445,9 +1448,6 @@ int wsg_reply_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_
 }
 
 namespace {
-
-// upper bound of the pieces: sum of ceil((size + 15) / PIECE) over frames
-inline uint64_t pieces_bound(uint32_t n, uint64_t wire_cap) { return wire_cap / wsg::PIECE + 2 * uint64_t(n) + 1; }
 
 // Small-frame batches (average frame <= small_avg) take k_encode_small,
 // the rest the piece kernel.

@@ -1,5 +1,6 @@
-// wsg_internal.h — kernel geometry and kernel declarations shared by
-// wsg_kernels.hip and the C-ABI implementation.
+// wsg_internal.h — kernel geometry and kernel declarations shared by the
+// kernel sources (wsg_kernels.hip, wsg_messages.hip, wsg_frames.hip,
+// wsg_utf8.hip) and the C-ABI implementation.
 #pragma once
 
 #include "wsg_frame.h"
@@ -47,7 +48,8 @@ __global__ void k_decode(const uint8_t* wire, uint8_t* out, uint64_t wire_len, c
                          uint64_t num_tiles);
 __global__ void k_xor(const uint8_t* src, uint8_t* dst, uint64_t len, uint32_t key, uint32_t phase);
 
-// Host launchers (defined in wsg_kernels.hip next to the kernels).
+// Host launchers, each defined next to its kernels: in wsg_kernels.hip unless
+// its section names another source.
 // One-launch decode (k_decode): grid blocks over the wire's tiles, per-frame
 // info and the error latch from the same launch.
 hipError_t launch_decode(hipStream_t s, int grid, const uint8_t* wire, uint8_t* out, uint64_t wire_len,
@@ -68,7 +70,7 @@ hipError_t launch_encode_scan_small(hipStream_t s, const wsg_send_desc* desc, ui
 hipError_t launch_encode_small(hipStream_t s, const uint8_t* payload, const wsg_send_desc* desc, uint32_t n,
                                uint64_t* wire_off, const uint64_t* scan, uint8_t* wire, uint64_t wire_cap,
                                unsigned long long* err);
-// ---- message assembly (wsg_decode_messages) --------------------------------
+// ---- message assembly (wsg_decode_messages; wsg_messages.hip) ---------------
 // Plan scratch of one call, carved by the host out of one device block
 // (msg_plan_layout): per-frame scan results, per-block partials (one block =
 // BLOCK frames), the totals.
@@ -122,7 +124,7 @@ hipError_t launch_msg_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_len
 hipError_t launch_msg_gather(hipStream_t s, int grid, const uint8_t* wire, const MsgPlan& plan,
                              const MsgPiece* pieces, uint64_t pieces_cap, uint8_t* msg, uint64_t msg_cap);
 
-// ---- replies (wsg_reply_messages) -------------------------------------------
+// ---- replies (wsg_reply_messages; wsg_messages.hip) -------------------------
 // The caller's rule, by value in the kernels' arguments.
 struct ReplyRule {
     uint8_t op[5];   // by WSG_CB_*: the reply's first header byte, 0 (none) or WSG_REPLY_SAME
@@ -142,7 +144,7 @@ hipError_t launch_reply_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_l
 hipError_t launch_reply_gather(hipStream_t s, int grid, const uint8_t* wire, const MsgPlan& plan,
                                const MsgPiece* pieces, uint64_t pieces_cap, uint8_t* reply, uint64_t reply_cap);
 
-// ---- the device framer (wsg_frame_streams) ---------------------------------
+// ---- the device framer (wsg_frame_streams; wsg_frames.hip) -----------------
 // Scratch of one call, carved out of one device array of uint64 (one block =
 // BLOCK streams).
 struct FramePlan {
@@ -167,7 +169,7 @@ hipError_t launch_frame_streams(hipStream_t s, int grid, const uint8_t* wire, ui
 hipError_t launch_frame_tail(hipStream_t s, wsg_stream_span* span, uint32_t ns, const uint64_t* frame_start,
                              const uint32_t* stream_first, const wsg_stream_state* state, uint32_t n);
 
-// ---- UTF-8 on the device (wsg_check_utf8) -----------------------------------
+// ---- UTF-8 on the device (wsg_check_utf8; wsg_utf8.hip) ---------------------
 // k_utf8_init: d_valid[m] = len for m < min(d_count[0], msg_room), and
 // d_result = {0, UINT64_MAX, 0, 0} (grid >= 1 also when msg_room == 0).
 hipError_t launch_utf8_init(hipStream_t s, int grid, const wsg_msg* msgs, const uint64_t* count, uint32_t msg_room,
@@ -182,6 +184,7 @@ hipError_t launch_utf8_scan(hipStream_t s, int grid, const uint8_t* msg, uint64_
 hipError_t launch_utf8_count(hipStream_t s, int grid, const wsg_msg* msgs, const uint64_t* count, uint32_t msg_room,
                              uint64_t msg_cap, uint32_t which, const uint64_t* valid, uint64_t* result);
 
+// ---- fan-out, XOR, offset rebase, test hook (wsg_kernels.hip) ---------------
 // Messages of one fan-out launch (blockIdx.y): payload and output offsets.
 constexpr int FAN_MSGS = 32;
 struct FanMsgs {

@@ -21,24 +21,19 @@
 //   staged   - more frames (small frames): segments staged in LDS, 256
 //              frames per round.
 // No MFMA: XOR is not a contraction; the bound is HBM bandwidth.
-#include "wsg_internal.h"
-#include "wsg_utf8.h"
+// Also here: the fan-out and the host lane, which calls the decode's and the
+// small-frame encode's helpers.  The stages around a decoded batch are in
+// wsg_messages.hip, wsg_frames.hip and wsg_utf8.hip.
+#include "wsg_device.h"
 
 namespace wsg {
 
 namespace {
 
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 typedef uint64_t v4u64 __attribute__((ext_vector_type(4)));   // MAXF-wide frame fields
 
 constexpr int MAXF = 4;   // frames a tile may touch and still take the boundary path
 
-// Streaming loads/stores carry the nontemporal hint (measured faster for
-// once-touched data on MI355X: tools/membench.hip); WSG_NT_LOAD/STORE=0
-// builds the plain-policy variants for A/B runs.
-#ifndef WSG_NT_LOAD
-#define WSG_NT_LOAD 1
-#endif
 #ifndef WSG_ENC_NT_SRC
 #define WSG_ENC_NT_SRC 0   // encode payload loads: plain policy measured 1-5% faster than nontemporal
 #endif
@@ -91,10 +86,7 @@ constexpr int MAXF = 4;   // frames a tile may touch and still take the boundary
 #ifndef WSG_FAN_KV
 #define WSG_FAN_KV 2   // fan-out period path: key registers per lane (64 pass-window slots each)
 #endif
-#ifndef WSG_NT_STORE
-#define WSG_NT_STORE 1
-#endif
-__device__ __forceinline__ v4u ld16(const uint8_t* p) { return *reinterpret_cast<const v4u*>(p); }
+
 // 16 bytes of host memory in one request past the GPU's caches (the system
 // scope of the relaxed atomic loads, sc0 sc1): one snapshot of the 16 bytes.
 __device__ __forceinline__ v4u ld16_sys(const void* p)
@@ -102,19 +94,6 @@ __device__ __forceinline__ v4u ld16_sys(const void* p)
     v4u r;
     asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1\n\ts_waitcnt vmcnt(0)" : "=v"(r) : "v"(p) : "memory");
     return r;
-}
-__device__ __forceinline__ v4u ld16nt(const uint8_t* p)
-{
-    if (WSG_NT_LOAD)
-        return __builtin_nontemporal_load(reinterpret_cast<const v4u*>(p));
-    return ld16(p);
-}
-__device__ __forceinline__ void st16nt(uint8_t* p, v4u v)
-{
-    if (WSG_NT_STORE)
-        __builtin_nontemporal_store(v, reinterpret_cast<v4u*>(p));
-    else
-        *reinterpret_cast<v4u*>(p) = v;
 }
 
 // Stores of a once-written output stream.  Write-through (sc1) buffer stores
@@ -156,77 +135,11 @@ struct OutTile {
     }
 };
 
-__device__ __forceinline__ uint32_t ab(uint32_t hi, uint32_t lo, uint32_t b)
-{
-    return __builtin_amdgcn_alignbyte(hi, lo, b);   // ({hi,lo} >> 8b)[31:0]
-}
-
-// Bytes [s, s+16) of the 32-byte little-endian window lo:hi (v_alignbyte_b32).
-__device__ __forceinline__ v4u funnel(v4u lo, v4u hi, uint32_t s)
-{
-    const uint32_t b = s & 3u;
-    v4u r;
-    switch (s >> 2) {
-    case 0:
-        r = v4u{ab(lo.y, lo.x, b), ab(lo.z, lo.y, b), ab(lo.w, lo.z, b), ab(hi.x, lo.w, b)};
-        break;
-    case 1:
-        r = v4u{ab(lo.z, lo.y, b), ab(lo.w, lo.z, b), ab(hi.x, lo.w, b), ab(hi.y, hi.x, b)};
-        break;
-    case 2:
-        r = v4u{ab(lo.w, lo.z, b), ab(hi.x, lo.w, b), ab(hi.y, hi.x, b), ab(hi.z, hi.y, b)};
-        break;
-    default:
-        r = v4u{ab(hi.x, lo.w, b), ab(hi.y, hi.x, b), ab(hi.z, hi.y, b), ab(hi.w, hi.z, b)};
-        break;
-    }
-    return r;
-}
-
-// 16 source bytes at an arbitrary address, read as aligned 16-B blocks
-// (never touching a 16-B block that holds no requested byte).
-template <bool NT>
-__device__ __forceinline__ v4u ld16_unaligned(const uint8_t* a)
-{
-    const uint32_t s = uint32_t(reinterpret_cast<uintptr_t>(a) & 15u);
-    const uint8_t* a0 = a - s;
-    const v4u lo = NT ? ld16nt(a0) : ld16(a0);
-    if (s == 0)
-        return lo;
-    return funnel(lo, NT ? ld16nt(a0 + 16) : ld16(a0 + 16), s);
-}
-
-// Byte j (runtime) of a 16-byte value, through two 64-bit halves so that no
-// register array is indexed at run time (that would spill to scratch).
-__device__ __forceinline__ uint32_t lane_byte(v4u v, uint32_t j)
-{
-    const uint64_t lo = uint64_t(v.x) | (uint64_t(v.y) << 32);
-    const uint64_t hi = uint64_t(v.z) | (uint64_t(v.w) << 32);
-    return uint32_t((j < 8 ? lo >> (8u * j) : hi >> (8u * (j - 8))) & 0xFFu);
-}
-
-__device__ __forceinline__ void put_byte(v4u& w, uint32_t j, uint32_t b)
-{
-    const uint64_t m = uint64_t(b & 0xFFu) << (8u * (j & 7u));
-    const uint64_t lo = j < 8 ? m : 0, hi = j < 8 ? 0 : m;
-    w.x |= uint32_t(lo);
-    w.y |= uint32_t(lo >> 32);
-    w.z |= uint32_t(hi);
-    w.w |= uint32_t(hi >> 32);
-}
-
 #ifndef WSG_STAGE_FPL
 #define WSG_STAGE_FPL 2
 #endif
 constexpr int SPL = WSG_STAGE_FPL;   // staged frames per lane per round
 constexpr int LDSF = BLOCK * SPL;    // frames per staged round (one round for tiles of 32-byte frames)
-
-__device__ __forceinline__ uint64_t lane_bcast(uint64_t v, int src)
-{
-    const uint32_t lo = __builtin_amdgcn_readlane(uint32_t(v), src);
-    const uint32_t hi = __builtin_amdgcn_readlane(uint32_t(v >> 32), src);
-    return uint64_t(lo) | (uint64_t(hi) << 32);
-}
 
 // map[t] = frame for t in [lo, hi) (encode: piece -> frame), for every lane's range, with the
 // whole wave storing each range (one lane per frame would serialise a large
@@ -251,39 +164,6 @@ __device__ __forceinline__ void fill_tiles_wave(uint32_t* tile_first, uint64_t l
 
 __device__ __forceinline__ uint64_t lane_off(int u) { return (uint64_t(u) * BLOCK + threadIdx.x) * CHUNK; }
 
-// ---- wave / block exclusive scan of uint64 (wave64) ----------------------
-__device__ __forceinline__ uint64_t wave_inclusive_scan(uint64_t v)
-{
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t u = __shfl_up(v, d, 64);
-        if (lane >= d)
-            v += u;
-    }
-    return v;
-}
-
-// Exclusive scan over the block (blockDim.x == BLOCK); *total = block sum.
-__device__ uint64_t block_exclusive_scan(uint64_t v, uint64_t* total)
-{
-    __shared__ uint64_t wsum[BLOCK / 64];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const uint64_t inc = wave_inclusive_scan(v);
-    if (lane == 63)
-        wsum[wid] = inc;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-#pragma unroll
-    for (int k = 0; k < BLOCK / 64; ++k) {
-        before += (k < wid) ? wsum[k] : 0;
-        all += wsum[k];
-    }
-    __syncthreads();
-    *total = all;
-    return before + inc - v;
-}
-
 } // namespace
 
 // ===========================================================================
@@ -306,86 +186,6 @@ __device__ uint64_t block_exclusive_scan(uint64_t v, uint64_t* total)
 // in LDS, LDSF frames per round).
 
 namespace {
-
-// A wave-uniform value computed by vector instructions, moved to SGPRs.
-__device__ __forceinline__ uint32_t uni(uint32_t x) { return __builtin_amdgcn_readfirstlane(x); }
-// (the builtins return int: each half goes through uint32_t, else a low half
-// of 2^31 or more sign-extends over the high one)
-__device__ __forceinline__ uint64_t uni(uint64_t x)
-{
-    return uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(uint32_t(x)))) |
-           (uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(uint32_t(x >> 32)))) << 32);
-}
-
-// Frame [s, limit) as PrepareReceiveFrame parses it when delivered whole
-// (ws.cpp:320-386), with the batch checks of wsg_decode_batch.  Returns 0 or
-// the frame's error; on error r describes an empty payload at s, so the
-// frame's bytes are copied.
-// (Block16: the aligned 16-byte block at a wire offset; global memory here,
-// LDS for the host lane's staged wire.)
-template <class Block16>
-__device__ __forceinline__ int frame_parse_b(Block16 block, uint64_t wire_len, uint64_t s, uint64_t limit,
-                                             wsg_recv_info& r)
-{
-    r = wsg_recv_info{};
-    int e = WSG_ETRUNC;
-    if (s < wire_len) {
-        const uint64_t avail = wire_len - s;
-        // wire[s .. s+16) as two u64 from the aligned 32-byte window, with
-        // 64-bit shifts only (scalar instructions when s is wave-uniform)
-        const uint64_t a0 = s & ~uint64_t(15);
-        const v4u lo = block(a0);
-        const v4u hi = (a0 + 16 < wire_len) ? block(a0 + 16) : v4u{0, 0, 0, 0};
-        uint64_t q0 = uint64_t(lo.x) | (uint64_t(lo.y) << 32), q1 = uint64_t(lo.z) | (uint64_t(lo.w) << 32);
-        const uint64_t q2 = uint64_t(hi.x) | (uint64_t(hi.y) << 32), q3 = uint64_t(hi.z) | (uint64_t(hi.w) << 32);
-        uint64_t q2s = q2;
-        if (s & 8) {
-            q0 = q1;
-            q1 = q2;
-            q2s = q3;
-        }
-        const uint32_t b = 8u * uint32_t(s & 7);
-        const uint64_t h0 = b ? (q0 >> b) | (q1 << (64u - b)) : q0;
-        const uint64_t h1 = b ? (q1 >> b) | (q2s << (64u - b)) : q1;
-        e = parse_header([&](uint32_t k) { return uint8_t(k < 8 ? h0 >> (8u * k) : h1 >> (8u * (k - 8))); }, avail, r);
-        if (e == 0) {
-            if (r.len > avail - r.hdr_len)
-                e = WSG_ETRUNC;
-            else if (limit < s || limit - s < r.hdr_len || r.len > limit - s - r.hdr_len)
-                e = WSG_EINVAL;   // the next frame starts inside this one
-        }
-    }
-    if (e != 0) {
-        r = wsg_recv_info{};
-        r.payload_off = s;
-        r.error = int8_t(e);
-    } else {
-        r.payload_off = s + r.hdr_len;
-    }
-    return e;
-}
-
-__device__ __forceinline__ int frame_parse(const uint8_t* __restrict__ wire, uint64_t wire_len, uint64_t s,
-                                           uint64_t limit, wsg_recv_info& r)
-{
-    return frame_parse_b([wire](uint64_t a) { return ld16(wire + a); }, wire_len, s, limit, r);
-}
-
-// wsg_recv_info as four 8-byte words (a struct store of the byte fields went
-// through scratch).
-__device__ __forceinline__ void store_info(wsg_recv_info* dst, const wsg_recv_info& r)
-{
-    static_assert(offsetof(wsg_recv_info, key) == 16 && offsetof(wsg_recv_info, opcode) == 20 &&
-                      offsetof(wsg_recv_info, b0) == 24 && offsetof(wsg_recv_info, error) == 25 &&
-                      sizeof(wsg_recv_info) == 32,
-                  "wsg_recv_info layout");
-    uint64_t* w = reinterpret_cast<uint64_t*>(dst);
-    w[0] = r.payload_off;
-    w[1] = r.len;
-    w[2] = uint64_t(r.key) | (uint64_t(r.opcode) << 32) | (uint64_t(r.fin) << 40) | (uint64_t(r.masked) << 48) |
-           (uint64_t(r.hdr_len) << 56);
-    w[3] = uint64_t(r.b0) | (uint64_t(uint8_t(r.error)) << 8);
-}
 
 __device__ __forceinline__ uint64_t fs_at(const uint64_t* __restrict__ fs, uint32_t n, int64_t i)
 {
@@ -499,12 +299,6 @@ __device__ __forceinline__ Seg tile_seg(uint64_t po, uint64_t pe, uint32_t key, 
         s.hi = s.lo;   // empty stays at its place: segment ends stay sorted
     s.kr = key_rot(key, uint32_t(base - po));   // (base - po) mod 4, also when po > base
     return s;
-}
-
-// Bytes [0, k) of a dword as a mask (k <= 0: none, k >= 4: all).
-__device__ __forceinline__ uint32_t low_bytes(int k)
-{
-    return k <= 0 ? 0u : k >= 4 ? ~0u : (1u << (8 * k)) - 1u;
 }
 
 // The XOR word of segment s for the chunk at tile offset o (zero outside s).
@@ -775,7 +569,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WSG_DEC_W
                 wsg_recv_info r;
                 const int e = frame_parse(wire, wire_len, fs[i], i + 1 < n ? fs[i + 1] : wire_len, r);
                 if (e != 0)
-                    atomicMin(err, (static_cast<unsigned long long>(i) << 8) | static_cast<unsigned long long>(-e));
+                    latch(err, i, e);
                 store_info(info + i, r);
             }
         }
@@ -826,42 +620,6 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WSG_DEC_W
 
 namespace {
 
-// Everything a piece needs about its frame (wave-uniform).
-struct FrameRec {
-    uint64_t off;       // wire offset of the frame
-    uint64_t pw;        // wire offset of the payload (status prefix included)
-    uint64_t data_w;    // wire offset of the first data byte
-    uint64_t end;       // wire offset one past the frame
-    const uint8_t* src; // data bytes
-    uint64_t body;
-    uint32_t key;
-    uint32_t hdr;
-    uint32_t prefix;
-    int32_t status;
-    uint8_t opcode;
-    bool mask;
-};
-
-__device__ __forceinline__ FrameRec make_rec(uint64_t off, const uint8_t* src, uint64_t len, uint32_t key,
-                                             int32_t status, uint8_t opcode, bool mask)
-{
-    const SendGeom g = send_geom(opcode, mask, len, status);
-    FrameRec r;
-    r.off = off;
-    r.pw = off + g.hdr;
-    r.data_w = r.pw + g.prefix;
-    r.end = r.pw + g.body;
-    r.src = src;
-    r.body = g.body;
-    r.key = key;
-    r.hdr = g.hdr;
-    r.prefix = g.prefix;
-    r.status = status;
-    r.opcode = opcode;
-    r.mask = mask;
-    return r;
-}
-
 // A descriptor read as eight dwords: scalar loads cannot fetch the u8 fields
 // on gfx9, and a vector load for them would bring an s_waitcnt vmcnt(0)
 // that also waits for every data load in flight.
@@ -889,38 +647,12 @@ static_assert(offsetof(wsg_send_desc, key) == 16 && offsetof(wsg_send_desc, opco
                   offsetof(wsg_send_desc, mask) == 25,
               "wsg_send_desc layout");
 
-__device__ __forceinline__ uint32_t wave_id() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
-
-// 16 payload bytes as seen from a chunk: byte j = payload[c + j] where that
-// offset is inside [0, len) (else 0).  Reads only aligned 16-B blocks that
-// hold a wanted byte, at most two.
-// The 16-B block at an aligned address: a global load, or (the lane) the
-// block's copy staged in LDS.
-struct GlobalBlocks {
-    __device__ v4u operator()(const uint8_t* p) const { return ld16(p); }
-};
+// fan_window's blocks for the host lane: the payload's copy staged in LDS.
 struct StagedBlocks {
     const v4u* s;          // LDS copy of the aligned blocks from `base` on
     const uint8_t* base;   // 16-B aligned
     __device__ v4u operator()(const uint8_t* p) const { return s[(p - base) >> 4]; }
 };
-
-template <class Blocks = GlobalBlocks>
-__device__ __forceinline__ v4u fan_window(const uint8_t* __restrict__ payload, uint64_t len, int64_t c,
-                                          Blocks blk = Blocks{})
-{
-    // offsets relative to `payload`, loads through pointer arithmetic on it
-    // (global_* loads; a pointer rebuilt from an integer loads flat_*)
-    const uint32_t s = uint32_t((reinterpret_cast<uintptr_t>(payload) + uint64_t(c)) & 15u);
-    const int64_t r0 = c - int64_t(s);   // aligned block holding byte c, relative to payload
-    const int64_t n = int64_t(len);
-    v4u lo = {0, 0, 0, 0}, hi = {0, 0, 0, 0};
-    if (r0 < n && r0 + 16 > 0)
-        lo = blk(payload + r0);
-    if (s != 0 && r0 + 16 < n && r0 + 32 > 0)
-        hi = blk(payload + r0 + 16);
-    return s ? funnel(lo, hi, s) : lo;
-}
 
 // 128-bit byte shifts and byte masks (runtime counts) built on funnel().
 __device__ __forceinline__ v4u shr_bytes(v4u x, uint64_t o)   // byte j = x[j + o]
@@ -936,22 +668,6 @@ __device__ __forceinline__ v4u low_bytes(uint64_t n)   // bytes [0, n) = 0xFF
     const uint64_t lo = n >= 8 ? ~uint64_t(0) : (uint64_t(1) << (8 * n)) - 1;
     const uint64_t hi = n >= 16 ? ~uint64_t(0) : n <= 8 ? 0 : (uint64_t(1) << (8 * (n - 8))) - 1;
     return v4u{uint32_t(lo), uint32_t(lo >> 32), uint32_t(hi), uint32_t(hi >> 32)};
-}
-
-// Header + close-status bytes of frame R (<= 16, as PrepareSendFrame writes
-// them, the status masked like payload bytes 0-1: SURVEY Q2/Q3), zero past
-// them; wave-uniform.
-__device__ __forceinline__ v4u frame_head(const FrameRec& R)
-{
-    v4u h = {0, 0, 0, 0};
-#pragma unroll 1
-    for (uint32_t r = 0; r < R.hdr; ++r)
-        put_byte(h, r, header_byte(R.opcode, R.mask, R.body, R.key, r));
-    if (R.prefix) {
-        put_byte(h, R.hdr, uint32_t((R.status >> 8) & 0xFF) ^ key_byte(R.key, 0));
-        put_byte(h, R.hdr + 1, uint32_t(R.status & 0xFF) ^ key_byte(R.key, 1));
-    }
-    return h;
 }
 
 // edge_chunk built with 16-byte vector operations instead of a byte loop:
@@ -1095,10 +811,10 @@ __global__ __launch_bounds__(BLOCK) void k_encode_scan_local(const wsg_send_desc
     for (int k = 0; k < SCAN_PER_LANE; ++k) {
         const uint64_t i = first + uint64_t(k) * BLOCK + threadIdx.x;
         uint64_t tot, tot_p = 0;
-        const uint64_t ex = block_exclusive_scan(sz[k], &tot);
+        const uint64_t ex = block_scan_ex(sz[k], OpAdd{}, &tot);
         uint64_t ex_p = 0;
         if (PIECES)
-            ex_p = block_exclusive_scan(sz[k] ? pieces_of(sz[k]) : 0, &tot_p);
+            ex_p = block_scan_ex(sz[k] ? pieces_of(sz[k]) : 0, OpAdd{}, &tot_p);
         if (i < n) {
             wire_off[i] = run + ex;
             if (PIECES)
@@ -1123,19 +839,8 @@ __global__ __launch_bounds__(BLOCK) void k_encode_scan_blocks(const uint64_t* __
                                                               uint64_t* __restrict__ wire_off,
                                                               uint32_t* __restrict__ piece_start, uint32_t n)
 {
-    uint64_t carry = 0, carry_p = 0;
-    for (uint32_t c = 0; c < nb; c += BLOCK) {
-        const uint32_t i = c + threadIdx.x;
-        uint64_t tot, tot_p;
-        const uint64_t ex = block_exclusive_scan(i < nb ? block_sums[i] : 0, &tot);
-        const uint64_t ex_p = block_exclusive_scan(i < nb ? block_psums[i] : 0, &tot_p);
-        if (i < nb) {
-            block_prefix[i] = carry + ex;
-            block_pprefix[i] = carry_p + ex_p;
-        }
-        carry += tot;
-        carry_p += tot_p;
-    }
+    const uint64_t carry = scan_partials(block_sums, block_prefix, nb, OpAdd{});
+    const uint64_t carry_p = scan_partials(block_psums, block_pprefix, nb, OpAdd{});
     if (threadIdx.x == 0) {
         wire_off[n] = carry;
         piece_start[n] = uint32_t(carry_p);
@@ -1164,10 +869,8 @@ __global__ __launch_bounds__(BLOCK) void k_encode_finalize(const wsg_send_desc* 
         wire_off[i] = off;
         piece_start[i] = uint32_t(ps);
         if (end > wire_cap)
-            atomicMin(err, (static_cast<unsigned long long>(i) << 8) |
-                               static_cast<unsigned long long>(-WSG_ENOMEM));
-        lo = min(ps, pieces_cap);
-        hi = min(ps + pieces_of(g.hdr + g.body), pieces_cap);
+            latch(err, i, WSG_ENOMEM);
+        piece_range(ps, ps + pieces_of(g.hdr + g.body), pieces_cap, lo, hi);
     }
     fill_tiles_wave(piece_frame, lo, hi, i);
 }
@@ -1434,8 +1137,8 @@ __global__ __launch_bounds__(BLOCK) void k_encode_small(const uint8_t* __restric
         before += k < sb ? v : 0;
     }
     uint64_t prefix, total;
-    (void)block_exclusive_scan(before, &prefix);
-    (void)block_exclusive_scan(all, &total);
+    (void)block_scan_ex(before, OpAdd{}, &prefix);
+    (void)block_scan_ex(all, OpAdd{}, &total);
     if (blockIdx.x == 0 && t == 0)
         wire_off[n] = total;
     const bool over = total > wire_cap;
@@ -1448,8 +1151,7 @@ __global__ __launch_bounds__(BLOCK) void k_encode_small(const uint8_t* __restric
         if (t + 1 == cnt)
             s_off[cnt] = end;   // not from wire_off[i + 1]: the next block may have finalized it already
         if (end > wire_cap)
-            atomicMin(err, (static_cast<unsigned long long>(i) << 8) |
-                               static_cast<unsigned long long>(-WSG_ENOMEM));
+            latch(err, i, WSG_ENOMEM);
     }
     __syncthreads();
     if (over)
@@ -2408,1402 +2110,6 @@ hipError_t launch_xor(hipStream_t s, int grid, const uint8_t* src, uint8_t* dst,
                       uint32_t phase)
 {
     k_xor<<<grid, BLOCK, 0, s>>>(src, dst, len, key, phase);
-    return hipGetLastError();
-}
-
-// ===========================================================================
-// Message assembly: wsg_decode_messages
-// ===========================================================================
-//
-// The second half of PrepareReceiveFrame (ws.cpp:399-452) over a batch whose
-// frames are grouped into streams: every FIN frame ends a message made of the
-// unmasked payloads of its stream's frames since the previous FIN frame, and
-// the messages are packed back to back into one buffer.
-//
-// Plan pass, one lane per frame (BLOCK frames per block, block partials
-// scanned by one block in between):
-//   k_msg_scan_local   header parse (d_info, error latch), the frame's stream,
-//                      and three block-local scans: FIN frames before i (sum),
-//                      last frame <= i that heads a stream or names an opcode
-//                      (max: the sticky _ws_opcode), last FIN frame < i (max:
-//                      where i's message began)
-//   k_msg_scan_blocks  the three over the block partials; d_count[0]
-//   k_msg_bytes_local  a frame is delivered when its stream has a FIN frame
-//                      at or after it; block-local sums of delivered bytes
-//                      (the frame's offset in d_msg) and of pieces
-//   k_msg_bytes_blocks those over the block partials; d_count[1]; WSG_ENOMEM
-//   k_msg_finalize     FIN lanes write their wsg_msg; the gather's piece records
-//   k_msg_state        one lane per stream: consumed, _ws_opcode
-// Gather pass (k_msg_gather), the mirror of k_encode_mask: a piece is at most
-// PIECE bytes of ONE frame's payload cut at absolute 16-byte chunks of the
-// DESTINATION (rows on 128-byte lines), one wave per piece, so the key, the
-// key phase (byte index in the frame's payload mod 4) and the source shift
-// are uniform over it.  Full chunks: one aligned 16-B nontemporal load per
-// lane, the second block of the 32-byte window taken from the next lane's
-// registers, v_alignbyte funnel, XOR, 16-B nontemporal store.  The two chunks a frame shares with its
-// neighbours in d_msg: each frame stores only its own bytes (neighbours run
-// in other waves).
-
-// k_msg_gather's source loads (tools/msgbench.py, one box, C2 / C3 in
-// fragments, us): a chunk's second 16-B block is the next lane's first, so
-// it comes from that lane's registers and every block is loaded once, with
-// the nontemporal hint: 90.8 / 731.  Loaded a second time instead (as
-// k_encode_mask does): 94.4 / 769 with plain first loads, 110.7 / 832 with
-// nontemporal ones (the second read then misses); shuffled but plain loads
-// 91.3 / 778.
-#ifndef WSG_MSG_SHFL
-#define WSG_MSG_SHFL 1    // the second block from the next lane's registers (0: a second load)
-#endif
-#ifndef WSG_MSG_NT_LO
-#define WSG_MSG_NT_LO 1   // nontemporal loads of a chunk's first source block
-#endif
-#ifndef WSG_MSG_NT_HI
-#define WSG_MSG_NT_HI 1   // ... and of a second block that is loaded
-#endif
-
-namespace {
-
-struct OpAdd {
-    template <class T>
-    __device__ __forceinline__ T operator()(T a, T b) const { return a + b; }
-};
-struct OpMax {
-    template <class T>
-    __device__ __forceinline__ T operator()(T a, T b) const { return a > b ? a : b; }
-};
-
-// Exclusive scan over the block under op (identity 0); *total = op over the
-// block.  The inclusive value is op(result, v).
-template <class T, class Op>
-__device__ T block_scan_ex(T v, Op op, T* total)
-{
-    __shared__ T wsum[BLOCK / 64];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    T inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T u = __shfl_up(inc, d, 64);
-        if (lane >= d)
-            inc = op(u, inc);
-    }
-    const T prev = __shfl_up(inc, 1, 64);
-    if (lane == 63)
-        wsum[wid] = inc;
-    __syncthreads();
-    T before = 0, all = 0;
-#pragma unroll
-    for (int k = 0; k < BLOCK / 64; ++k) {
-        if (k < wid)
-            before = op(before, wsum[k]);
-        all = op(all, wsum[k]);
-    }
-    __syncthreads();
-    *total = all;
-    return lane ? op(before, prev) : before;
-}
-
-// Last j < ns with sf[j] <= i (0 when there is none): the stream of frame i
-// (an empty stream shares its first index with the next one, which wins).
-__device__ __forceinline__ uint32_t stream_of(const uint32_t* __restrict__ sf, uint32_t ns, uint32_t i)
-{
-    uint32_t lo = 0, hi = ns;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (sf[mid] <= i)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
-// Batch-wide values of the plan's block-local scans, for k in [0, n].
-__device__ __forceinline__ uint64_t fins_before(const MsgPlan& P, uint32_t n, uint32_t k)
-{
-    return k < n ? uint64_t(P.finx[k]) + P.bfin_pre[k / BLOCK] : P.tot[0];
-}
-__device__ __forceinline__ uint32_t last_fin_before(const MsgPlan& P, uint32_t n, uint32_t k)   // + 1; 0: none
-{
-    return k < n ? max(P.qx[k], P.bq_pre[k / BLOCK]) : uint32_t(P.tot[1]);
-}
-__device__ __forceinline__ uint64_t dst_of(const MsgPlan& P, uint32_t k)   // k < n
-{
-    return P.dst[k] + P.bbytes_pre[k / BLOCK];
-}
-__device__ __forceinline__ uint64_t pieces_before(const MsgPlan& P, uint32_t n, uint32_t k)
-{
-    return k < n ? uint64_t(P.pstart[k]) + P.bpc_pre[k / BLOCK] : P.tot[3];
-}
-// _ws_opcode after frame i of stream j (ws.cpp:326): the last non-zero
-// opcode of the stream up to i, else the stream's seed.
-__device__ __forceinline__ uint32_t sticky_opcode(const MsgPlan& P, const wsg_recv_info* __restrict__ info,
-                                                  const wsg_stream_state* state, uint32_t i, uint32_t j)
-{
-    const uint32_t pv = max(P.pinc[i], P.bp_pre[i / BLOCK]);
-    const uint32_t op = pv ? info[pv - 1].opcode : 0u;
-    return op ? op : state[j].opcode;
-}
-
-__device__ __forceinline__ uint64_t msg_pieces_of(uint64_t bytes)
-{
-    return bytes ? (bytes + PIECE_ALIGN - 1 + PIECE - 1) / PIECE : 0;
-}
-
-__device__ __forceinline__ void put_piece(MsgPiece* p, uint64_t poff, uint64_t d0, uint64_t len, uint32_t key,
-                                          uint32_t k)
-{
-    static_assert(sizeof(MsgPiece) == 32 && offsetof(MsgPiece, len) == 16 && offsetof(MsgPiece, k) == 28, "MsgPiece");
-    v4u* w = reinterpret_cast<v4u*>(p);
-    w[0] = v4u{uint32_t(poff), uint32_t(poff >> 32), uint32_t(d0), uint32_t(d0 >> 32)};
-    w[1] = v4u{uint32_t(len), uint32_t(len >> 32), key, k};
-}
-
-// pieces[t] for t in [lo, hi) of every lane's frame (fill_tiles_wave's
-// scheme: a frame of many pieces is written by the whole wave).
-__device__ __forceinline__ void fill_pieces_wave(MsgPiece* pieces, uint64_t lo, uint64_t hi, uint64_t poff,
-                                                 uint64_t d0, uint64_t len, uint32_t key)
-{
-    const uint32_t lane = threadIdx.x & 63;
-    constexpr uint64_t kShort = 4;   // ranges up to this many pieces: the lane stores its own
-    if (hi > lo && hi - lo <= kShort)
-        for (uint64_t t = lo; t < hi; ++t)
-            put_piece(pieces + t, poff, d0, len, key, uint32_t(t - lo));
-    uint64_t pending = __ballot(hi > lo + kShort);
-    while (pending) {
-        const int j = __builtin_ctzll(pending);
-        pending &= pending - 1;
-        const uint64_t a = lane_bcast(lo, j), b = lane_bcast(hi, j);
-        const uint64_t pj = lane_bcast(poff, j), dj = lane_bcast(d0, j), lj = lane_bcast(len, j);
-        const uint32_t kj = __builtin_amdgcn_readlane(key, j);
-        for (uint64_t t = a + lane; t < b; t += 64)
-            put_piece(pieces + t, pj, dj, lj, kj, uint32_t(t - a));
-    }
-}
-
-
-// The message that FIN frame i ends (ws.cpp:411-452), as the wsg_msg fields.
-struct MsgRec {
-    uint64_t off, len;
-    uint32_t stream, first, kind, op;
-    int32_t status;
-};
-
-__device__ __forceinline__ MsgRec msg_at_fin(const uint8_t* __restrict__ wire, const wsg_recv_info* __restrict__ info,
-                                             uint32_t n, const uint32_t* __restrict__ sf,
-                                             const wsg_stream_state* __restrict__ state, const MsgPlan& P, uint32_t i,
-                                             uint64_t frame_len)
-{
-    const uint32_t j = P.sidx[i];
-    const uint32_t ff = min(max(last_fin_before(P, n, i), sf[j]), i);   // the message's first frame
-    const uint64_t base = dst_of(P, ff), end = dst_of(P, i) + frame_len;
-    const uint32_t op = sticky_opcode(P, info, state, i, j);
-    uint64_t off = base, len = end - base;
-    uint32_t kind = 0;
-    int32_t status = 0;
-    if (op == WSG_TEXT || op == WSG_BINARY) {
-        kind = WSG_CB_RECEIVED;
-    } else if (op == WSG_PING) {
-        kind = WSG_CB_PING;
-    } else if (op == WSG_PONG) {
-        kind = WSG_CB_PONG;
-    } else if (op == WSG_CLOSE) {
-        kind = WSG_CB_CLOSE;
-        status = 1000;
-        if (len >= 2) {   // ws.cpp:435-439: the buffer's first two bytes, wherever their frames are
-            uint32_t sb[2];
-            for (uint32_t t = 0; t < 2; ++t) {
-                const uint64_t x = base + t;
-                uint32_t a = ff, b = i + 1;   // last k in [ff, i] with dst_of(k) <= x holds byte x
-                while (b - a > 1) {
-                    const uint32_t mid = a + (b - a) / 2;
-                    if (dst_of(P, mid) <= x)
-                        a = mid;
-                    else
-                        b = mid;
-                }
-                const uint64_t o = x - dst_of(P, a);
-                // (o < len unless stream_first is malformed: never a read past the payload)
-                sb[t] = o < info[a].len ? uint32_t(wire[info[a].payload_off + o]) ^ key_byte(info[a].key, o) : 0u;
-            }
-            status = int32_t((sb[0] << 8) | sb[1]);
-            off += 2;
-            len -= 2;
-        }
-    }
-    return MsgRec{off, len, j, ff, kind, op, status};
-}
-
-__device__ __forceinline__ void put_msg(wsg_msg* m, const MsgRec& r, uint32_t last)
-{
-    static_assert(sizeof(wsg_msg) == 40 && offsetof(wsg_msg, stream) == 16 && offsetof(wsg_msg, nframes) == 24 &&
-                      offsetof(wsg_msg, status) == 28 && offsetof(wsg_msg, kind) == 32 &&
-                      offsetof(wsg_msg, opcode) == 33,
-                  "wsg_msg layout");
-    uint64_t* w = reinterpret_cast<uint64_t*>(m);
-    w[0] = r.off;
-    w[1] = r.len;
-    w[2] = uint64_t(r.stream) | (uint64_t(r.first) << 32);
-    w[3] = uint64_t(last - r.first + 1) | (uint64_t(uint32_t(r.status)) << 32);
-    w[4] = uint64_t(r.kind) | (uint64_t(r.op) << 8);
-}
-
-} // namespace
-
-__global__ __launch_bounds__(BLOCK) void k_msg_scan_local(const uint8_t* __restrict__ wire, uint64_t wire_len,
-                                                          const uint64_t* __restrict__ fs, uint32_t n,
-                                                          const uint32_t* __restrict__ sf, uint32_t ns,
-                                                          wsg_recv_info* __restrict__ info, MsgPlan P,
-                                                          unsigned long long* err)
-{
-    const uint64_t i64 = uint64_t(blockIdx.x) * BLOCK + threadIdx.x;
-    const uint32_t i = uint32_t(i64);
-    uint32_t fin = 0, pv = 0;
-    if (i64 < n) {
-        wsg_recv_info r;
-        const int e = frame_parse(wire, wire_len, fs[i], i + 1 < n ? fs[i + 1] : wire_len, r);
-        if (e != 0)
-            atomicMin(err, (static_cast<unsigned long long>(i) << 8) | static_cast<unsigned long long>(-e));
-        store_info(info + i, r);
-        const uint32_t j = stream_of(sf, ns, i);
-        P.sidx[i] = j;
-        fin = r.fin;
-        pv = (r.opcode != 0 || sf[j] == i) ? i + 1 : 0;
-    }
-    uint32_t tf, tp, tq;
-    const uint32_t ef = block_scan_ex(fin, OpAdd{}, &tf);
-    const uint32_t ep = block_scan_ex(pv, OpMax{}, &tp);
-    const uint32_t eq = block_scan_ex(fin ? i + 1 : 0u, OpMax{}, &tq);
-    if (i64 < n) {
-        P.finx[i] = ef;
-        P.pinc[i] = max(ep, pv);
-        P.qx[i] = eq;
-    }
-    if (threadIdx.x == 0) {
-        P.bfin[blockIdx.x] = tf;
-        P.bp[blockIdx.x] = tp;
-        P.bq[blockIdx.x] = tq;
-    }
-}
-
-__global__ __launch_bounds__(BLOCK) void k_msg_scan_blocks(MsgPlan P, uint32_t nb, uint64_t* __restrict__ count)
-{
-    uint32_t cf = 0, cp = 0, cq = 0;
-    for (uint32_t c = 0; c < nb; c += BLOCK) {
-        const uint32_t b = c + threadIdx.x;
-        uint32_t tf, tp, tq;
-        const uint32_t ef = block_scan_ex(b < nb ? P.bfin[b] : 0u, OpAdd{}, &tf);
-        const uint32_t ep = block_scan_ex(b < nb ? P.bp[b] : 0u, OpMax{}, &tp);
-        const uint32_t eq = block_scan_ex(b < nb ? P.bq[b] : 0u, OpMax{}, &tq);
-        if (b < nb) {
-            P.bfin_pre[b] = cf + ef;
-            P.bp_pre[b] = max(cp, ep);
-            P.bq_pre[b] = max(cq, eq);
-        }
-        cf += tf;
-        cp = max(cp, tp);
-        cq = max(cq, tq);
-    }
-    if (threadIdx.x == 0) {
-        P.tot[0] = cf;
-        P.tot[1] = cq;
-        count[0] = cf;
-    }
-}
-
-__global__ __launch_bounds__(BLOCK) void k_msg_bytes_local(const wsg_recv_info* __restrict__ info, uint32_t n,
-                                                           const uint32_t* __restrict__ sf, MsgPlan P)
-{
-    const uint64_t i64 = uint64_t(blockIdx.x) * BLOCK + threadIdx.x;
-    const uint32_t i = uint32_t(i64);
-    uint64_t dl = 0;
-    if (i64 < n) {
-        const uint32_t end = min(sf[P.sidx[i] + 1], n);
-        if (fins_before(P, n, end) > fins_before(P, n, i))   // a FIN frame in [i, end): not in the tail
-            dl = info[i].len;
-    }
-    uint64_t tb, tp;
-    const uint64_t eb = block_scan_ex(dl, OpAdd{}, &tb);
-    const uint64_t ep = block_scan_ex(msg_pieces_of(dl), OpAdd{}, &tp);
-    if (i64 < n) {
-        P.dst[i] = eb;
-        P.pstart[i] = uint32_t(ep);
-    }
-    if (threadIdx.x == 0) {
-        P.bbytes[blockIdx.x] = tb;
-        P.bpc[blockIdx.x] = tp;
-    }
-}
-
-__global__ __launch_bounds__(BLOCK) void k_msg_bytes_blocks(MsgPlan P, uint32_t nb, uint32_t n, uint64_t msg_cap,
-                                                            uint64_t* __restrict__ count, unsigned long long* err)
-{
-    uint64_t cb = 0, cp = 0;
-    for (uint32_t c = 0; c < nb; c += BLOCK) {
-        const uint32_t b = c + threadIdx.x;
-        uint64_t tb, tp;
-        const uint64_t eb = block_scan_ex(b < nb ? P.bbytes[b] : uint64_t(0), OpAdd{}, &tb);
-        const uint64_t ep = block_scan_ex(b < nb ? P.bpc[b] : uint64_t(0), OpAdd{}, &tp);
-        if (b < nb) {
-            P.bbytes_pre[b] = cb + eb;
-            P.bpc_pre[b] = cp + ep;
-        }
-        cb += tb;
-        cp += tp;
-    }
-    if (threadIdx.x == 0) {
-        P.tot[2] = cb;
-        P.tot[3] = cp;
-        count[1] = cb;
-        if (cb > msg_cap)   // behind every frame error: the latch keeps the smallest
-            atomicMin(err, (static_cast<unsigned long long>(n) << 8) | static_cast<unsigned long long>(-WSG_ENOMEM));
-    }
-}
-
-__global__ __launch_bounds__(BLOCK) void k_msg_finalize(const uint8_t* __restrict__ wire,
-                                                        const wsg_recv_info* __restrict__ info, uint32_t n,
-                                                        const uint32_t* __restrict__ sf,
-                                                        const wsg_stream_state* __restrict__ state, MsgPlan P,
-                                                        wsg_msg* __restrict__ msgs,
-                                                        MsgPiece* __restrict__ pieces, uint64_t pieces_cap)
-{
-    if (uint64_t(blockIdx.x) * BLOCK + (threadIdx.x & ~63u) >= n)
-        return;   // whole wave past the last frame
-    const uint64_t i64 = uint64_t(blockIdx.x) * BLOCK + threadIdx.x;
-    const uint32_t i = uint32_t(i64);
-    uint64_t lo = 0, hi = 0, poff = 0, d0 = 0, plen = 0;
-    uint32_t key = 0;
-    if (i64 < n) {
-        lo = min(pieces_before(P, n, i), pieces_cap);
-        hi = min(pieces_before(P, n, i + 1), pieces_cap);
-        if (hi < lo)
-            hi = lo;
-        const wsg_recv_info r = info[i];
-        poff = r.payload_off;
-        plen = r.len;
-        key = r.key;
-        d0 = dst_of(P, i);
-        if (r.fin)
-            put_msg(msgs + fins_before(P, n, i), msg_at_fin(wire, info, n, sf, state, P, i, r.len), i);
-    }
-    fill_pieces_wave(pieces, lo, hi, poff, d0, plen, key);
-}
-
-__global__ __launch_bounds__(BLOCK) void k_msg_state(const wsg_recv_info* __restrict__ info, uint32_t n,
-                                                     const uint32_t* __restrict__ sf, uint32_t ns,
-                                                     wsg_stream_state* state, MsgPlan P)
-{
-    static_assert(sizeof(wsg_stream_state) == 8 && offsetof(wsg_stream_state, opcode) == 4, "wsg_stream_state layout");
-    const uint64_t j64 = uint64_t(blockIdx.x) * BLOCK + threadIdx.x;
-    if (j64 >= ns)
-        return;
-    const uint32_t j = uint32_t(j64);
-    const uint32_t start = min(sf[j], n), end = max(min(sf[j + 1], n), start);
-    uint32_t consumed = 0, op = state[j].opcode;
-    if (fins_before(P, n, end) > fins_before(P, n, start)) {
-        const uint32_t last = last_fin_before(P, n, end);   // + 1: in (start, end]
-        if (last > start && last <= end) {
-            consumed = last - start;
-            op = sticky_opcode(P, info, state, last - 1, j);
-        }
-    }
-    *reinterpret_cast<uint64_t*>(state + j) = uint64_t(consumed) | (uint64_t(op & 0xFFu) << 32);
-}
-
-// ---- replies (wsg_reply_messages) -------------------------------------------
-// The plan above up to k_msg_bytes_blocks, then, one lane per frame again:
-//   k_reply_local     FIN lanes write their wsg_msg and size the reply frame
-//                     (send_geom); block-local sums of the reply sizes.  The
-//                     sum over the FIN frames before frame i is the reply
-//                     offset of the message frame i belongs to, FIN or not.
-//   k_reply_blocks    those over the block partials; d_count[2..3]; the
-//                     capacity latch; the gather's totals (P.rtot)
-//   k_reply_finalize  FIN lanes: d_reply_off, header and status prefix (byte
-//                     stores, frame_head's bytes); every lane: its frame's
-//                     piece records with the reply wire as destination and
-//                     the receive key XOR the send key at the destination's
-//                     phase; a lane per stream: d_stream_reply
-// and k_msg_gather over those records: every payload byte is read once from
-// the received wire and written once, re-keyed, into its reply frame.
-
-namespace {
-
-// What message r is answered with: the first header byte (0: nothing), the
-// data length and the status of the PrepareSendFrame call.
-struct ReplyOf {
-    uint8_t op;
-    uint64_t len;
-    int32_t status;
-};
-
-__device__ __forceinline__ ReplyOf reply_of(const ReplyRule& rule, uint32_t kind, uint32_t opcode, uint64_t len,
-                                            int32_t status)
-{
-    const uint8_t v = kind >= 1 && kind <= 4 ? rule.op[kind] : uint8_t(0);
-    ReplyOf r;
-    r.op = v == WSG_REPLY_SAME ? uint8_t(WSG_FIN | opcode) : v;
-    r.len = kind == WSG_CB_CLOSE ? 0 : len;   // a close reply carries the status and no data
-    r.status = kind == WSG_CB_CLOSE ? status : 0;
-    return r;
-}
-
-__device__ __forceinline__ uint64_t reply_size(const ReplyRule& rule, const ReplyOf& r)
-{
-    if (!r.op)
-        return 0;
-    const SendGeom g = send_geom(r.op, rule.mask != 0, r.len, r.status);
-    return g.hdr + g.body;
-}
-
-// Reply bytes of the FIN frames before frame k, for k in [0, n].
-__device__ __forceinline__ uint64_t reply_before(const MsgPlan& P, uint32_t n, uint32_t k)
-{
-    return k < n ? P.rex[k] + P.brep_pre[k / BLOCK] : P.rtot[2];
-}
-
-} // namespace
-
-__global__ __launch_bounds__(BLOCK) void k_reply_local(const uint8_t* __restrict__ wire,
-                                                       const wsg_recv_info* __restrict__ info, uint32_t n,
-                                                       const uint32_t* __restrict__ sf,
-                                                       const wsg_stream_state* __restrict__ state, MsgPlan P,
-                                                       ReplyRule rule, wsg_msg* __restrict__ msgs)
-{
-    const uint64_t i64 = uint64_t(blockIdx.x) * BLOCK + threadIdx.x;
-    const uint32_t i = uint32_t(i64);
-    uint64_t size = 0;
-    if (i64 < n && info[i].fin) {
-        const MsgRec m = msg_at_fin(wire, info, n, sf, state, P, i, info[i].len);
-        put_msg(msgs + fins_before(P, n, i), m, i);
-        size = reply_size(rule, reply_of(rule, m.kind, m.op, m.len, m.status));
-    }
-    uint64_t tb, tn;
-    const uint64_t eb = block_scan_ex(size, OpAdd{}, &tb);
-    block_scan_ex(uint64_t(size != 0), OpAdd{}, &tn);
-    if (i64 < n)
-        P.rex[i] = eb;
-    if (threadIdx.x == 0) {
-        P.brep[blockIdx.x] = tb;
-        P.brn[blockIdx.x] = tn;
-    }
-}
-
-__global__ __launch_bounds__(BLOCK) void k_reply_blocks(MsgPlan P, uint32_t nb, uint32_t n, uint64_t reply_cap,
-                                                        uint64_t* __restrict__ count, unsigned long long* err)
-{
-    uint64_t cb = 0, cn = 0;
-    for (uint32_t c = 0; c < nb; c += BLOCK) {
-        const uint32_t b = c + threadIdx.x;
-        uint64_t tb, tn;
-        const uint64_t eb = block_scan_ex(b < nb ? P.brep[b] : uint64_t(0), OpAdd{}, &tb);
-        block_scan_ex(b < nb ? P.brn[b] : uint64_t(0), OpAdd{}, &tn);
-        if (b < nb)
-            P.brep_pre[b] = cb + eb;
-        cb += tb;
-        cn += tn;
-    }
-    if (threadIdx.x == 0) {
-        P.rtot[2] = cb;         // k_msg_gather's view of the totals: bytes against the capacity,
-        P.rtot[3] = P.tot[3];   // and the piece count
-        count[2] = cb;
-        count[3] = cn;
-        if (cb > reply_cap)   // behind every frame error: the latch keeps the smallest
-            atomicMin(err, (static_cast<unsigned long long>(n) << 8) | static_cast<unsigned long long>(-WSG_ENOMEM));
-    }
-}
-
-__global__ __launch_bounds__(BLOCK) void k_reply_finalize(const wsg_recv_info* __restrict__ info, uint32_t n,
-                                                          const uint32_t* __restrict__ sf, uint32_t ns, MsgPlan P,
-                                                          ReplyRule rule, const uint32_t* __restrict__ send_key,
-                                                          const wsg_msg* __restrict__ msgs,
-                                                          uint8_t* __restrict__ reply, uint64_t reply_cap,
-                                                          uint64_t* __restrict__ reply_off,
-                                                          uint64_t* __restrict__ stream_reply,
-                                                          MsgPiece* __restrict__ pieces, uint64_t pieces_cap)
-{
-    const uint64_t i64 = uint64_t(blockIdx.x) * BLOCK + threadIdx.x;
-    const uint32_t i = uint32_t(i64);
-    const uint64_t total = P.rtot[2], nmsg = P.tot[0];
-    // connection j's replies start where its first message's does
-    for (uint64_t j = i64; j <= ns; j += uint64_t(gridDim.x) * BLOCK)
-        stream_reply[j] = reply_before(P, n, min(sf[j], n));
-    if (i64 == 0)
-        reply_off[nmsg] = total;
-    uint64_t lo = 0, hi = 0, poff = 0, d0 = 0, plen = 0;
-    uint32_t key = 0;
-    if (i64 < n) {
-        lo = min(pieces_before(P, n, i), pieces_cap);
-        hi = min(pieces_before(P, n, i + 1), pieces_cap);
-        if (hi < lo)
-            hi = lo;
-        const wsg_recv_info r = info[i];
-        const uint64_t m = fins_before(P, n, i);
-        if ((r.fin || hi > lo) && m < nmsg) {   // frame i belongs to message m
-            const uint32_t* w = reinterpret_cast<const uint32_t*>(msgs + m);
-            const uint64_t moff = uint64_t(w[0]) | (uint64_t(w[1]) << 32);
-            const uint64_t mlen = uint64_t(w[2]) | (uint64_t(w[3]) << 32);
-            const uint32_t j = w[4], kind = w[8] & 0xFFu, opcode = (w[8] >> 8) & 0xFFu;
-            const ReplyOf a = reply_of(rule, kind, opcode, mlen, int32_t(w[7]));
-            const uint64_t at = reply_before(P, n, i);
-            const uint32_t skey = send_key ? send_key[j] : 0u;
-            if (r.fin)
-                reply_off[m] = at;
-            if (a.op) {
-                const FrameRec R = make_rec(at, nullptr, a.len, skey, a.status, a.op, rule.mask != 0);
-                if (r.fin && total <= reply_cap) {
-                    const v4u h = frame_head(R);
-                    for (uint32_t t = 0; t < R.hdr + R.prefix; ++t)
-                        reply[at + t] = uint8_t(lane_byte(h, t));
-                }
-                // data byte dst_of(i) - moff of the message: c bytes into the reply's payload
-                // (inside the message unless stream_first is malformed: never a store outside the frame)
-                const uint64_t rel = dst_of(P, i) - moff;
-                if (a.len && dst_of(P, i) >= moff && rel <= a.len && r.len <= a.len - rel) {
-                    const uint64_t c = R.prefix + rel;
-                    poff = r.payload_off;
-                    plen = r.len;
-                    d0 = R.pw + c;
-                    key = r.key ^ key_rot(skey, uint32_t(c));
-                }
-            }
-        }
-    }
-    // (a frame whose message gets no data keeps d0 = plen = 0: its pieces are empty)
-    fill_pieces_wave(pieces, lo, hi, poff, d0, plen, key);
-}
-
-__global__ __launch_bounds__(BLOCK) void k_msg_gather(const uint8_t* __restrict__ wire,
-                                                      const uint64_t* __restrict__ tot,
-                                                      const MsgPiece* __restrict__ piece_recs, uint64_t pieces_cap,
-                                                      uint8_t* __restrict__ msg, uint64_t msg_cap)
-{
-    const uint64_t waves = uint64_t(gridDim.x) * (BLOCK / 64);
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t q0 = uint64_t(blockIdx.x) * (BLOCK / 64) + wave_id();
-    if (tot[2] > msg_cap)
-        return;   // WSG_ENOMEM latched by k_msg_bytes_blocks: no byte of msg
-    const uint64_t pieces = min(tot[3], pieces_cap);
-    for (uint64_t q = q0; q < pieces; q += waves) {
-        // the record as dwords (wave-uniform: one scalar load, as load_desc)
-        const uint32_t* w = reinterpret_cast<const uint32_t*>(piece_recs + q);
-        const uint64_t poff = uint64_t(w[0]) | (uint64_t(w[1]) << 32);
-        const uint64_t d0 = uint64_t(w[2]) | (uint64_t(w[3]) << 32);
-        const uint64_t len = uint64_t(w[4]) | (uint64_t(w[5]) << 32);
-        const uint32_t key = w[6];
-        const uint64_t k = w[7];
-        const uint64_t end = d0 + len;
-        const uint64_t lo = (d0 & ~(PIECE_ALIGN - 1)) + k * PIECE;
-        if (lo >= end || end > msg_cap)
-            continue;   // piece counts are an upper bound
-        const uint64_t hi = min(lo + PIECE, end);
-        // source of msg byte p: src + (p - d0), as pointer arithmetic on the
-        // wire argument (global_* loads)
-        const uint8_t* src = wire + poff;
-        const uint32_t s = uint32_t((reinterpret_cast<uintptr_t>(src) + (lo - d0)) & 15u);
-        const uint32_t kw = key_rot(key, uint32_t(lo - d0));   // phase: byte index in the payload (mod 4 also when lo < d0)
-        v4u a[EU], b[EU];
-        uint32_t full = 0;
-#pragma unroll
-        for (int u = 0; u < EU; ++u) {
-            const uint64_t p = lo + (uint64_t(u) * 64 + lane) * CHUNK;
-            const bool f = p < hi && p >= d0 && p + CHUNK <= end;
-            full |= uint32_t(f) << u;
-            const uint8_t* a0 = src + (int64_t(p - d0) - int64_t(s));
-            a[u] = f ? (WSG_MSG_NT_LO ? ld16nt(a0) : ld16(a0)) : v4u{0, 0, 0, 0};
-        }
-#if !WSG_MSG_SHFL
-#pragma unroll
-        for (int u = 0; u < EU; ++u) {
-            const uint64_t p = lo + (uint64_t(u) * 64 + lane) * CHUNK;
-            const uint8_t* a0 = src + (int64_t(p - d0) - int64_t(s));
-            b[u] = ((full >> u) & 1u) && s ? (WSG_MSG_NT_HI ? ld16nt(a0 + CHUNK) : ld16(a0 + CHUNK)) : v4u{0, 0, 0, 0};
-        }
-#else
-        // bit u: the lane after this one in the piece (lane 0 of the next row
-        // for lane 63) loaded the block after a[u] as its own first block
-        const uint32_t nfull = lane == 63 ? uint32_t(__builtin_amdgcn_readlane(full, 0)) >> 1
-                                          : uint32_t(__shfl_down(full, 1, 64));
-#pragma unroll
-        for (int u = 0; u < EU; ++u) {
-            const uint64_t p = lo + (uint64_t(u) * 64 + lane) * CHUNK;
-            const uint8_t* a0 = src + (int64_t(p - d0) - int64_t(s));
-            b[u] = ((full >> u) & 1u) && s && !((nfull >> u) & 1u)
-                       ? (WSG_MSG_NT_HI ? ld16nt(a0 + CHUNK) : ld16(a0 + CHUNK))
-                       : v4u{0, 0, 0, 0};
-        }
-        if (s) {
-#pragma unroll
-            for (int u = 0; u < EU; ++u) {
-                v4u nx;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const uint32_t first = u + 1 < EU ? uint32_t(__builtin_amdgcn_readlane(a[u + 1 < EU ? u + 1 : u][c], 0)) : 0u;
-                    const uint32_t down = uint32_t(__shfl_down(a[u][c], 1, 64));
-                    nx[c] = lane == 63 ? first : down;
-                }
-                if ((nfull >> u) & 1u)
-                    b[u] = nx;
-            }
-        }
-#endif
-        // the full chunks first, in a straight line: with the edge chunks'
-        // loads and byte stores between them every store waited for the one
-        // before it (stores count in vmcnt on gfx9)
-#pragma unroll
-        for (int u = 0; u < EU; ++u)
-            a[u] = (s ? funnel(a[u], b[u], s) : a[u]) ^ kw;
-#pragma unroll
-        for (int u = 0; u < EU; ++u) {
-            const uint64_t p = lo + (uint64_t(u) * 64 + lane) * CHUNK;
-            if ((full >> u) & 1u)
-                st16nt(msg + p, a[u]);
-        }
-        // the (at most two) chunks shared with a neighbour frame: this
-        // frame's bytes only; wave-uniform test, most pieces have none
-        const bool head_edge = lo <= d0 && (d0 & (CHUNK - 1)) != 0;
-        const bool tail_edge = hi == end && (end & (CHUNK - 1)) != 0;
-        if (!head_edge && !tail_edge)
-            continue;
-#pragma unroll 1
-        for (uint32_t u = 0; u < uint32_t(EU); ++u) {
-            const uint64_t p = lo + (uint64_t(u) * 64 + lane) * CHUNK;
-            if (((full >> u) & 1u) || p >= hi || p + CHUNK <= d0)
-                continue;
-            const v4u v = fan_window(src, len, int64_t(p) - int64_t(d0)) ^ kw;
-            const uint32_t o_lo = p < d0 ? uint32_t(d0 - p) : 0u;
-            const uint32_t o_hi = end - p < CHUNK ? uint32_t(end - p) : uint32_t(CHUNK);
-            uint32_t* m32 = reinterpret_cast<uint32_t*>(msg + p);
-#pragma unroll
-            for (uint32_t c = 0; c < 4; ++c) {
-                const uint32_t b0 = 4 * c, b1 = b0 + 4;
-                if (b0 >= o_lo && b1 <= o_hi) {
-                    m32[c] = v[c];
-                } else {
-                    for (uint32_t t = max(b0, o_lo); t < min(b1, o_hi); ++t)
-                        msg[p + t] = uint8_t(v[c] >> (8 * (t - b0)));
-                }
-            }
-        }
-    }
-}
-
-uint64_t msg_plan_layout(uint8_t* base, uint32_t n, MsgPlan* plan)
-{
-    const uint64_t nb = (uint64_t(n) + BLOCK - 1) / BLOCK;
-    uint64_t at = 0;
-    auto take = [&](uint64_t bytes) {
-        uint8_t* p = base + at;
-        at += (bytes + 15) & ~uint64_t(15);
-        return p;
-    };
-    MsgPlan P;
-    P.dst = reinterpret_cast<uint64_t*>(take(uint64_t(n) * 8));
-    P.bbytes = reinterpret_cast<uint64_t*>(take(nb * 8));
-    P.bbytes_pre = reinterpret_cast<uint64_t*>(take(nb * 8));
-    P.bpc = reinterpret_cast<uint64_t*>(take(nb * 8));
-    P.bpc_pre = reinterpret_cast<uint64_t*>(take(nb * 8));
-    P.tot = reinterpret_cast<uint64_t*>(take(4 * 8));
-    P.finx = reinterpret_cast<uint32_t*>(take(uint64_t(n) * 4));
-    P.pinc = reinterpret_cast<uint32_t*>(take(uint64_t(n) * 4));
-    P.qx = reinterpret_cast<uint32_t*>(take(uint64_t(n) * 4));
-    P.sidx = reinterpret_cast<uint32_t*>(take(uint64_t(n) * 4));
-    P.pstart = reinterpret_cast<uint32_t*>(take(uint64_t(n) * 4));
-    P.bfin = reinterpret_cast<uint32_t*>(take(nb * 4));
-    P.bfin_pre = reinterpret_cast<uint32_t*>(take(nb * 4));
-    P.bp = reinterpret_cast<uint32_t*>(take(nb * 4));
-    P.bp_pre = reinterpret_cast<uint32_t*>(take(nb * 4));
-    P.bq = reinterpret_cast<uint32_t*>(take(nb * 4));
-    P.bq_pre = reinterpret_cast<uint32_t*>(take(nb * 4));
-    P.rex = reinterpret_cast<uint64_t*>(take(uint64_t(n) * 8));
-    P.brep = reinterpret_cast<uint64_t*>(take(nb * 8));
-    P.brep_pre = reinterpret_cast<uint64_t*>(take(nb * 8));
-    P.brn = reinterpret_cast<uint64_t*>(take(nb * 8));
-    P.rtot = reinterpret_cast<uint64_t*>(take(4 * 8));
-    if (plan)
-        *plan = P;
-    return at;
-}
-
-hipError_t launch_msg_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
-                           const uint32_t* stream_first, uint32_t n_streams, wsg_stream_state* state, uint64_t msg_cap,
-                           wsg_msg* msgs, uint64_t* count, wsg_recv_info* info, const MsgPlan& plan,
-                           MsgPiece* pieces, uint64_t pieces_cap, unsigned long long* err)
-{
-    const uint32_t nb = uint32_t((uint64_t(n) + BLOCK - 1) / BLOCK);
-    if (n == 0) {   // no frame: no message, every stream unchanged with nothing consumed
-        if (hipError_t e = hipMemsetAsync(plan.tot, 0, 4 * sizeof(uint64_t), s); e != hipSuccess)
-            return e;
-        if (hipError_t e = hipMemsetAsync(count, 0, 2 * sizeof(uint64_t), s); e != hipSuccess)
-            return e;
-    } else {
-        k_msg_scan_local<<<nb, BLOCK, 0, s>>>(wire, wire_len, fs, n, stream_first, n_streams, info, plan, err);
-        k_msg_scan_blocks<<<1, BLOCK, 0, s>>>(plan, nb, count);
-        k_msg_bytes_local<<<nb, BLOCK, 0, s>>>(info, n, stream_first, plan);
-        k_msg_bytes_blocks<<<1, BLOCK, 0, s>>>(plan, nb, n, msg_cap, count, err);
-        k_msg_finalize<<<nb, BLOCK, 0, s>>>(wire, info, n, stream_first, state, plan, msgs, pieces, pieces_cap);
-    }
-    if (n_streams)
-        k_msg_state<<<(n_streams + BLOCK - 1) / BLOCK, BLOCK, 0, s>>>(info, n, stream_first, n_streams, state, plan);
-    return hipGetLastError();
-}
-
-hipError_t launch_msg_gather(hipStream_t s, int grid, const uint8_t* wire, const MsgPlan& plan,
-                             const MsgPiece* pieces, uint64_t pieces_cap, uint8_t* msg, uint64_t msg_cap)
-{
-    k_msg_gather<<<grid, BLOCK, 0, s>>>(wire, plan.tot, pieces, pieces_cap, msg, msg_cap);
-    return hipGetLastError();
-}
-
-hipError_t launch_reply_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
-                             const uint32_t* stream_first, uint32_t n_streams, wsg_stream_state* state,
-                             const ReplyRule& rule, const uint32_t* send_key, uint8_t* reply, uint64_t reply_cap,
-                             uint64_t* reply_off, uint64_t* stream_reply, wsg_msg* msgs, uint64_t* count,
-                             wsg_recv_info* info, const MsgPlan& plan, MsgPiece* pieces, uint64_t pieces_cap,
-                             unsigned long long* err)
-{
-    const uint32_t nb = uint32_t((uint64_t(n) + BLOCK - 1) / BLOCK);
-    if (n == 0) {   // no frame: no message, no reply, every stream unchanged with nothing consumed
-        if (hipError_t e = hipMemsetAsync(plan.tot, 0, 4 * sizeof(uint64_t), s); e != hipSuccess)
-            return e;
-        if (hipError_t e = hipMemsetAsync(plan.rtot, 0, 4 * sizeof(uint64_t), s); e != hipSuccess)
-            return e;
-        if (hipError_t e = hipMemsetAsync(count, 0, 4 * sizeof(uint64_t), s); e != hipSuccess)
-            return e;
-        if (hipError_t e = hipMemsetAsync(reply_off, 0, sizeof(uint64_t), s); e != hipSuccess)
-            return e;
-        if (hipError_t e = hipMemsetAsync(stream_reply, 0, (uint64_t(n_streams) + 1) * sizeof(uint64_t), s);
-            e != hipSuccess)
-            return e;
-    } else {
-        k_msg_scan_local<<<nb, BLOCK, 0, s>>>(wire, wire_len, fs, n, stream_first, n_streams, info, plan, err);
-        k_msg_scan_blocks<<<1, BLOCK, 0, s>>>(plan, nb, count);
-        k_msg_bytes_local<<<nb, BLOCK, 0, s>>>(info, n, stream_first, plan);
-        // (no d_msg: its size, d_count[1], meets no capacity)
-        k_msg_bytes_blocks<<<1, BLOCK, 0, s>>>(plan, nb, n, UINT64_MAX, count, err);
-        k_reply_local<<<nb, BLOCK, 0, s>>>(wire, info, n, stream_first, state, plan, rule, msgs);
-        k_reply_blocks<<<1, BLOCK, 0, s>>>(plan, nb, n, reply_cap, count, err);
-        k_reply_finalize<<<nb, BLOCK, 0, s>>>(info, n, stream_first, n_streams, plan, rule, send_key, msgs, reply,
-                                              reply_cap, reply_off, stream_reply, pieces, pieces_cap);
-    }
-    if (n_streams)
-        k_msg_state<<<(n_streams + BLOCK - 1) / BLOCK, BLOCK, 0, s>>>(info, n, stream_first, n_streams, state, plan);
-    return hipGetLastError();
-}
-
-hipError_t launch_reply_gather(hipStream_t s, int grid, const uint8_t* wire, const MsgPlan& plan,
-                               const MsgPiece* pieces, uint64_t pieces_cap, uint8_t* reply, uint64_t reply_cap)
-{
-    k_msg_gather<<<grid, BLOCK, 0, s>>>(wire, plan.rtot, pieces, pieces_cap, reply, reply_cap);
-    return hipGetLastError();
-}
-
-// ---- the device framer (wsg_frame_streams) ---------------------------------
-// Frame boundaries are sequential within a connection and independent across
-// connections: one wave walks one stream (grid-stride over streams).  Dense
-// output needs every stream's count before a start can be written, so the
-// streams are walked twice with a scan between: k_frame_count (consumed, need,
-// count, span errors), k_frame_scan_local / k_frame_scan_blocks (exclusive
-// prefix of the counts, d_count, the capacity latch), k_frame_write (the same
-// walk again, its lines now in L2, storing the starts).
-//
-// The walk (frame_walk): the wave keeps a window of its stream in LDS, a ring
-// of two halves of FR_HALF bytes, one aligned 16-B block per lane per half,
-// lanes past the span's end loading nothing.  Plain loads: k_decode reads
-// these lines next.  While half k is walked, half k + 1 is in the ring too (a
-// header that starts in half k ends there at the latest) and half k + 2 is in
-// flight in registers; it goes into half k's place once the position has left
-// half k.  The position is wave-uniform: the header bytes parse_header asks
-// for are read from the ring one by one (every lane the same LDS address, a
-// broadcast read; one byte decides a short frame) and carried in scalar
-// registers through uni().  A frame that ends beyond
-// the ring is a jump: the ring is re-based at the new position (one memory
-// round trip) and the payload between is never loaded.  The 64 most recent
-// starts wait in the lanes (lane i the i-th) and leave in one 512-byte store.
-//
-// Limits: one stream's walk is serial (an LDS round trip and some sixty
-// mostly scalar instructions per frame), so a batch that is one connection of tiny
-// frames is latency-bound on one wave, and one long stream among short ones
-// is the launch's critical path.
-
-namespace {
-
-constexpr uint32_t FR_HALF = 64 * CHUNK;          // 1 KiB: a 16-B block per lane
-constexpr uint32_t FR_BLOCKS = 2 * FR_HALF / 16;  // 16-B blocks of a wave's ring
-static_assert((FR_BLOCKS & (FR_BLOCKS - 1)) == 0 && FR_HALF >= 32, "the ring index is a mask; a header spans two blocks");
-
-struct SpanIn {
-    uint64_t off, len;
-    bool ok;
-};
-
-// Span j as given and whether it may be walked: inside the wire, and not
-// starting before the end of span j - 1 where that one lies inside the wire.
-__device__ __forceinline__ SpanIn span_in(const wsg_stream_span* span, uint32_t j, uint64_t wire_len)
-{
-    static_assert(sizeof(wsg_stream_span) == 32 && offsetof(wsg_stream_span, consumed) == 16, "wsg_stream_span layout");
-    const uint64_t* w = reinterpret_cast<const uint64_t*>(span + j);
-    SpanIn s;
-    s.off = uni(w[0]);
-    s.len = uni(w[1]);
-    bool ok = s.off <= wire_len && s.len <= wire_len - s.off;
-    if (ok && j > 0) {
-        const uint64_t* p = reinterpret_cast<const uint64_t*>(span + (j - 1));
-        const uint64_t poff = uni(p[0]), plen = uni(p[1]);
-        if (poff <= wire_len && plen <= wire_len - poff && s.off < poff + plen)
-            ok = false;
-    }
-    s.ok = uni(uint32_t(ok)) != 0;
-    return s;
-}
-
-// The aligned 16-B block at wire offset a, nothing for a block past `end`
-// (end <= wire_len, and the wire is readable to the end of its last block).
-__device__ __forceinline__ v4u fr_load(const uint8_t* __restrict__ wire, uint64_t a, uint64_t end)
-{
-    return a < end ? ld16(wire + a) : v4u{0, 0, 0, 0};
-}
-
-// Walk the whole frames of wire[off, end).  WRITE: store at most max_frames
-// starts to out[0..).  Every argument is wave-uniform.
-template <bool WRITE>
-__device__ __forceinline__ void frame_walk(const uint8_t* __restrict__ wire, uint64_t off, uint64_t end, v4u* ring,
-                                           uint64_t* __restrict__ out, uint64_t max_frames, uint64_t& consumed,
-                                           uint64_t& need, uint64_t& count)
-{
-    const uint32_t lane = threadIdx.x & 63;
-    uint64_t pos = off, cnt = 0, mine = 0;
-    uint64_t base = 0;   // wire offset of ring block 0 (16-B aligned)
-    uint64_t hs = 0;     // start of the half being walked; [hs, hs + 2 * FR_HALF) is in the ring
-    v4u pre = v4u{0, 0, 0, 0};   // the half behind those, in flight
-    bool fresh = true;
-    need = 0;
-    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(ring);
-    bool done = false;
-    while (!done) {
-        if (pos == end)   // need = 0
-            break;
-        if (fresh || pos - hs >= 2 * uint64_t(FR_HALF)) {   // a jump: re-base the ring at pos
-            fresh = false;
-            base = hs = pos & ~uint64_t(15);
-            const uint64_t a = base + uint64_t(lane) * CHUNK;
-            const v4u v0 = fr_load(wire, a, end), v1 = fr_load(wire, a + FR_HALF, end);
-            pre = fr_load(wire, a + 2 * uint64_t(FR_HALF), end);
-            ring[lane] = v0;
-            ring[64 + lane] = v1;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        } else if (pos - hs >= FR_HALF) {   // left a half: the one in flight takes its place
-            ring[(uint32_t((hs - base) >> 4) + lane) & (FR_BLOCKS - 1)] = pre;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            hs += FR_HALF;
-            pre = fr_load(wire, hs + 2 * uint64_t(FR_HALF) + uint64_t(lane) * CHUNK, end);
-        }
-        // the frames that start in this half: nothing but LDS reads and
-        // scalar arithmetic (and, WRITE, a store every 64 frames) in here
-        const uint64_t lim = min(hs + FR_HALF, end);
-        while (pos < lim) {
-            const uint64_t rem = end - pos;
-            if (rem < 2) {
-                need = 2;
-                done = true;
-                break;
-            }
-            if (WRITE && cnt >= max_frames) {
-                done = true;
-                break;
-            }
-            // header bytes as parse_header asks for them: broadcast LDS reads
-            // of the ring ([hs, hs + 2 * FR_HALF) holds any header that starts
-            // before lim), each made a scalar
-            const uint32_t at = uint32_t(pos - base);
-            const auto byte_at = [&](uint32_t k) { return uint8_t(uni(uint32_t(bytes[(at + k) & (16 * FR_BLOCKS - 1)]))); };
-            wsg_recv_info r;
-            if (parse_header(byte_at, rem, r) != 0) {   // rem >= 2: the header is incomplete
-                need = header_len(byte_at(1));
-                done = true;
-                break;
-            }
-            const uint32_t hdr = r.hdr_len;
-            if (r.len > rem - hdr) {   // (no hdr + len: a 127-form length may be 2^64 - 1)
-                need = r.len > UINT64_MAX - hdr ? UINT64_MAX : hdr + r.len;
-                done = true;
-                break;
-            }
-            if (WRITE) {
-                if (lane == uint32_t(cnt & 63))
-                    mine = pos;
-                if ((cnt & 63) == 63)
-                    out[cnt - 63 + lane] = mine;
-            }
-            ++cnt;
-            pos += hdr + r.len;
-        }
-    }
-    if (WRITE && lane < uint32_t(cnt & 63))
-        out[(cnt & ~uint64_t(63)) + lane] = mine;
-    consumed = pos - off;
-    count = cnt;
-}
-
-} // namespace
-
-__global__ __launch_bounds__(BLOCK) void k_frame_count(const uint8_t* __restrict__ wire, uint64_t wire_len,
-                                                       wsg_stream_span* span, uint32_t ns, uint64_t* __restrict__ cnt,
-                                                       unsigned long long* err)
-{
-    __shared__ v4u s_ring[BLOCK / 64][FR_BLOCKS];
-    const uint64_t waves = uint64_t(gridDim.x) * (BLOCK / 64);
-    const uint32_t lane = threadIdx.x & 63, wid = wave_id();
-    for (uint64_t j64 = uint64_t(blockIdx.x) * (BLOCK / 64) + wid; j64 < ns; j64 += waves) {
-        const uint32_t j = uint32_t(j64);
-        const SpanIn s = span_in(span, j, wire_len);
-        uint64_t consumed = 0, need = 0, n = 0;
-        if (s.ok)
-            frame_walk<false>(wire, s.off, s.off + s.len, s_ring[wid], nullptr, 0, consumed, need, n);
-        if (lane == 0) {
-            if (!s.ok)
-                atomicMin(err, (static_cast<unsigned long long>(j) << 8) | static_cast<unsigned long long>(-WSG_EINVAL));
-            uint64_t* w = reinterpret_cast<uint64_t*>(span + j);
-            w[2] = consumed;
-            w[3] = need;
-            cnt[j] = n;
-        }
-    }
-}
-
-__global__ __launch_bounds__(BLOCK) void k_frame_scan_local(const wsg_stream_span* span, uint32_t ns, FramePlan P)
-{
-    const uint64_t j64 = uint64_t(blockIdx.x) * BLOCK + threadIdx.x;
-    uint64_t c = 0, k = 0;
-    if (j64 < ns) {
-        c = P.cnt[j64];
-        k = reinterpret_cast<const uint64_t*>(span + j64)[2];
-    }
-    uint64_t tc, tk;
-    const uint64_t ec = block_scan_ex(c, OpAdd{}, &tc);
-    (void)block_scan_ex(k, OpAdd{}, &tk);
-    if (j64 < ns)
-        P.ex[j64] = ec;
-    if (threadIdx.x == 0) {
-        P.bcnt[blockIdx.x] = tc;
-        P.bcons[blockIdx.x] = tk;
-    }
-}
-
-__global__ __launch_bounds__(BLOCK) void k_frame_scan_blocks(FramePlan P, uint32_t nb, uint32_t ns, uint32_t frame_cap,
-                                                             uint64_t* __restrict__ count, unsigned long long* err)
-{
-    uint64_t cc = 0, ck = 0;
-    for (uint32_t c = 0; c < nb; c += BLOCK) {
-        const uint32_t b = c + threadIdx.x;
-        uint64_t tc, tk;
-        const uint64_t ec = block_scan_ex(b < nb ? P.bcnt[b] : uint64_t(0), OpAdd{}, &tc);
-        (void)block_scan_ex(b < nb ? P.bcons[b] : uint64_t(0), OpAdd{}, &tk);
-        if (b < nb)
-            P.bpre[b] = cc + ec;
-        cc += tc;
-        ck += tk;
-    }
-    if (threadIdx.x == 0) {
-        P.tot[0] = cc;
-        P.tot[1] = ck;
-        count[0] = cc;
-        count[1] = ck;
-        // behind every span error: the latch keeps the smallest
-        if (cc > uint64_t(UINT32_MAX) - 1)
-            atomicMin(err, (static_cast<unsigned long long>(ns) << 8) | static_cast<unsigned long long>(-WSG_EINVAL));
-        else if (cc > frame_cap)
-            atomicMin(err, (static_cast<unsigned long long>(ns) << 8) | static_cast<unsigned long long>(-WSG_ENOMEM));
-    }
-}
-
-__global__ __launch_bounds__(BLOCK) void k_frame_write(const uint8_t* __restrict__ wire, uint64_t wire_len,
-                                                       const wsg_stream_span* span, uint32_t ns, FramePlan P,
-                                                       uint64_t* __restrict__ fs, uint32_t frame_cap,
-                                                       uint32_t* __restrict__ sf)
-{
-    __shared__ v4u s_ring[BLOCK / 64][FR_BLOCKS];
-    const uint64_t waves = uint64_t(gridDim.x) * (BLOCK / 64);
-    const uint32_t lane = threadIdx.x & 63, wid = wave_id();
-    const uint64_t total = uni(P.tot[0]);
-    // WSG_ENOMEM / WSG_EINVAL latched by k_frame_scan_blocks: no entry of fs
-    const bool fits = total <= frame_cap && total <= uint64_t(UINT32_MAX) - 1;
-    for (uint64_t j64 = uint64_t(blockIdx.x) * (BLOCK / 64) + wid; j64 < ns; j64 += waves) {
-        const uint32_t j = uint32_t(j64);
-        const uint64_t first = uni(P.ex[j] + P.bpre[j / BLOCK]);
-        const uint64_t next = j64 + 1 < ns ? uni(P.ex[j + 1] + P.bpre[(j + 1) / BLOCK]) : total;
-        if (lane == 0) {
-            sf[j] = uint32_t(min(first, uint64_t(UINT32_MAX)));
-            if (j64 + 1 == ns)
-                sf[ns] = uint32_t(min(total, uint64_t(UINT32_MAX)));
-        }
-        if (!fits || next <= first)
-            continue;
-        const SpanIn s = span_in(span, j, wire_len);
-        if (!s.ok)
-            continue;
-        uint64_t consumed, need, n;
-        frame_walk<true>(wire, s.off, s.off + s.len, s_ring[wid], fs + first, next - first, consumed, need, n);
-    }
-}
-
-// One lane per stream.
-__global__ __launch_bounds__(BLOCK) void k_frame_tail(wsg_stream_span* span, uint32_t ns,
-                                                      const uint64_t* __restrict__ fs,
-                                                      const uint32_t* __restrict__ sf,
-                                                      const wsg_stream_state* __restrict__ state, uint32_t n)
-{
-    const uint64_t j64 = uint64_t(blockIdx.x) * BLOCK + threadIdx.x;
-    if (j64 >= ns)
-        return;
-    const uint32_t start = min(sf[j64], n), end = max(min(sf[j64 + 1], n), start);
-    const uint32_t used = state[j64].consumed;
-    if (used < end - start) {
-        uint64_t* w = reinterpret_cast<uint64_t*>(span + j64);
-        w[2] = fs[start + used] - w[0];
-    }
-}
-
-uint64_t frame_plan_layout(uint64_t* base, uint32_t ns, FramePlan* plan)
-{
-    const uint64_t nb = (uint64_t(ns) + BLOCK - 1) / BLOCK;
-    uint64_t at = 0;
-    auto take = [&](uint64_t entries) {
-        uint64_t* p = base + at;
-        at += entries;
-        return p;
-    };
-    FramePlan P;
-    P.cnt = take(ns);
-    P.ex = take(ns);
-    P.bcnt = take(nb);
-    P.bpre = take(nb);
-    P.bcons = take(nb);
-    P.tot = take(2);
-    if (plan)
-        *plan = P;
-    return at;
-}
-
-hipError_t launch_frame_streams(hipStream_t s, int grid, const uint8_t* wire, uint64_t wire_len, wsg_stream_span* span,
-                                uint32_t ns, uint64_t* frame_start, uint32_t frame_cap, uint32_t* stream_first,
-                                uint64_t* count, const FramePlan& plan, unsigned long long* err)
-{
-    if (ns == 0) {   // no stream: no frame
-        if (hipError_t e = hipMemsetAsync(count, 0, 2 * sizeof(uint64_t), s); e != hipSuccess)
-            return e;
-        return hipMemsetAsync(stream_first, 0, sizeof(uint32_t), s);
-    }
-    const uint32_t nb = uint32_t((uint64_t(ns) + BLOCK - 1) / BLOCK);
-    k_frame_count<<<grid, BLOCK, 0, s>>>(wire, wire_len, span, ns, plan.cnt, err);
-    k_frame_scan_local<<<nb, BLOCK, 0, s>>>(span, ns, plan);
-    k_frame_scan_blocks<<<1, BLOCK, 0, s>>>(plan, nb, ns, frame_cap, count, err);
-    k_frame_write<<<grid, BLOCK, 0, s>>>(wire, wire_len, span, ns, plan, frame_start, frame_cap, stream_first);
-    return hipGetLastError();
-}
-
-hipError_t launch_frame_tail(hipStream_t s, wsg_stream_span* span, uint32_t ns, const uint64_t* frame_start,
-                             const uint32_t* stream_first, const wsg_stream_state* state, uint32_t n)
-{
-    if (ns == 0 || n == 0)
-        return hipSuccess;
-    k_frame_tail<<<(ns + BLOCK - 1) / BLOCK, BLOCK, 0, s>>>(span, ns, frame_start, stream_first, state, n);
-    return hipGetLastError();
-}
-
-// ---- UTF-8 on the device (wsg_check_utf8) ----------------------------------
-// d_msg holds every message unmasked, its fragments joined: a text message
-// (or a close reason) is one byte string there, and whether a position of it
-// is bad depends on the 3 bytes before it and the 3 after (wsg_utf8.h).  So
-// the payload kernel is element-wise over the aligned 16-byte chunks of
-// d_msg[0, min(msg_cap, d_count[1])): one chunk per lane, one 16-B load, the
-// 4 bytes on either side from the neighbouring lanes' registers (the wave's
-// first and last lane load theirs).  A lane whose chunk holds no byte >= 0x80
-// has no bad position and does nothing more; a wave of such lanes goes on to
-// its next pass.  Otherwise the wave finds, with two searches of d_msgs
-// (message ends are non-decreasing; 64 probes a round, one per lane), the
-// records [mlo, mhi] its 1 KiB can touch, and each lane with a byte >= 0x80 walks the messages that overlap
-// its chunk: the next record whose end lies beyond the position reached (a
-// search inside [mlo, mhi], none when the wave lies in one message), so a run
-// of empty messages at one offset costs one step, and a chunk at most 16.
-// The bytes of the window outside the message in hand count as 00; the rule
-// of wsg_utf8.h is asked about the chunk word-wise (utf8_words_bad, some 80
-// VALU operations per 4 bytes), and only a lane it flags asks the
-// position-local form about its 16 positions; the lowest bad one goes to
-// d_valid[m] by atomicMin.  Valid text issues no
-// atomic.  k_utf8_init (d_valid[m] = len, d_result's seed) runs before it and
-// k_utf8_count (the four words of d_result) behind it, one lane per record.
-
-namespace {
-
-struct Utf8Rec {
-    uint64_t off, len, end;   // end: off + len, saturating
-    bool selected;
-};
-
-__device__ __forceinline__ Utf8Rec utf8_rec(const wsg_msg* __restrict__ msgs, uint32_t m, uint32_t which)
-{
-    static_assert(sizeof(wsg_msg) == 40 && offsetof(wsg_msg, len) == 8 && offsetof(wsg_msg, kind) == 32 &&
-                      offsetof(wsg_msg, opcode) == 33,
-                  "wsg_msg layout");
-    const uint64_t* w = reinterpret_cast<const uint64_t*>(msgs + m);
-    Utf8Rec r;
-    r.off = w[0];
-    r.len = w[1];
-    r.end = r.off + r.len < r.off ? UINT64_MAX : r.off + r.len;
-    const uint32_t kind = uint32_t(w[4]) & 0xFFu, opcode = (uint32_t(w[4]) >> 8) & 0xFFu;
-    r.selected = (which & WSG_UTF8_EVERY) || ((which & WSG_UTF8_TEXT) && kind == WSG_CB_RECEIVED && opcode == WSG_TEXT) ||
-                 ((which & WSG_UTF8_CLOSE) && kind == WSG_CB_CLOSE);
-    return r;
-}
-
-// off + len <= bound, without forming the sum
-__device__ __forceinline__ bool utf8_inside(const Utf8Rec& r, uint64_t bound)
-{
-    return r.len <= bound && r.off <= bound - r.len;
-}
-
-// First m in [lo, hi) whose end lies beyond pos; hi when there is none.
-__device__ __forceinline__ uint32_t utf8_first_beyond(const wsg_msg* __restrict__ msgs, uint32_t lo, uint32_t hi,
-                                                      uint64_t pos)
-{
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        const uint64_t* w = reinterpret_cast<const uint64_t*>(msgs + mid);
-        const uint64_t off = w[0], len = w[1];
-        const uint64_t end = off + len < off ? UINT64_MAX : off + len;
-        if (end > pos)
-            hi = mid;
-        else
-            lo = mid + 1;
-    }
-    return lo;
-}
-
-// The same answer for a wave-uniform pos, found by the whole wave: 64 probes a
-// round, the range shrinking 64-fold (two or three dependent loads where the
-// one-lane search takes log2 M of them; a wave's two searches per pass were
-// most of the time of non-ASCII text with the one-lane form).
-__device__ __forceinline__ uint32_t utf8_first_beyond_wave(const wsg_msg* __restrict__ msgs, uint32_t lo, uint32_t hi,
-                                                           uint64_t pos)
-{
-    const uint32_t lane = threadIdx.x & 63;
-    while (lo < hi) {   // the answer lies in [lo, hi]
-        const uint32_t step = (hi - lo + 63) / 64;
-        const uint64_t idx = uint64_t(lo) + uint64_t(lane) * step;
-        bool beyond = true;   // (a probe at or past hi counts as beyond)
-        if (idx < hi) {
-            const uint64_t* w = reinterpret_cast<const uint64_t*>(msgs + idx);
-            const uint64_t off = w[0], len = w[1];
-            beyond = (off + len < off ? UINT64_MAX : off + len) > pos;
-        }
-        const uint64_t b = __ballot(beyond);
-        const uint32_t f = b ? uint32_t(__builtin_ctzll(b)) : 64u;   // the first probe beyond pos
-        if (f == 0) {
-            hi = lo;
-        } else {   // behind probe f - 1, at or before probe f
-            const uint64_t top = uint64_t(lo) + uint64_t(f) * step;
-            lo = lo + (f - 1) * step + 1;
-            hi = top < hi ? uint32_t(top) : hi;
-        }
-    }
-    return lo;
-}
-
-// n < 16 bytes at p, one by one (the chunk the bound cuts: no byte at or past it is read)
-__device__ __forceinline__ v4u utf8_ld_partial(const uint8_t* __restrict__ p, uint32_t n)
-{
-    v4u r{0, 0, 0, 0};
-    for (uint32_t t = 0; t < n; ++t)
-        put_byte(r, t, p[t]);
-    return r;
-}
-
-// Bit i: chunk position i lies in [lo, hi) and is bad in the string whose
-// bytes are the window's bytes at the chunk-relative positions [lo, hi).  The
-// window: pre = positions -4..-1, c = 0..15, post = 16..19.
-__device__ __forceinline__ uint32_t utf8_chunk_bad(uint32_t pre, v4u c, uint32_t post, int lo, int hi)
-{
-    uint32_t d[6] = {pre, c.x, c.y, c.z, c.w, post};
-    // dword k holds the positions 4k - 4 .. 4k - 1: 00 outside [lo, hi)
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-        d[k] &= low_bytes(hi + 4 - 4 * k) & ~low_bytes(lo + 4 - 4 * k);
-    // word-wise first (wsg_utf8.h): valid text, the common case, ends here
-    uint32_t flags[4];
-    utf8_words_bad(d, flags);
-    if ((flags[0] | flags[1] | flags[2] | flags[3]) == 0)
-        return 0;
-    uint32_t by[22];   // positions -3..18 (constant indices once unrolled: registers)
-#pragma unroll
-    for (int j = 0; j < 22; ++j)
-        by[j] = (d[(j + 1) >> 2] >> (8 * ((j + 1) & 3))) & 0xFFu;
-    // (a position outside [lo, hi) now holds 00, an ASCII byte, never bad)
-    uint32_t bad = 0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        auto at = [&](int64_t k) { return by[k + 3]; };
-        if (by[i + 3] >= 0x80u && utf8_bad_at(at, int64_t(i)))
-            bad |= 1u << i;
-    }
-    return bad;
-}
-
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-        v += __shfl_down(v, d, 64);
-    return v;   // lane 0
-}
-
-__device__ __forceinline__ uint64_t wave_min(uint64_t v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint64_t u = __shfl_down(v, d, 64);
-        v = u < v ? u : v;
-    }
-    return v;   // lane 0
-}
-
-} // namespace
-
-// One lane per record (grid-stride): d_valid[m] = len; the first lane seeds
-// d_result = {0, UINT64_MAX, 0, 0} for k_utf8_count behind it.  (A kernel's
-// stores, not memsets: the call is meant to be captured, and the two memset
-// nodes this began with came back from a graph replay with other fill values.)
-__global__ __launch_bounds__(BLOCK) void k_utf8_init(const wsg_msg* __restrict__ msgs,
-                                                     const uint64_t* __restrict__ count, uint32_t msg_room,
-                                                     uint64_t* __restrict__ valid, uint64_t* __restrict__ result)
-{
-    if (blockIdx.x == 0 && threadIdx.x < 4)
-        result[threadIdx.x] = threadIdx.x == 1 ? UINT64_MAX : 0;
-    const uint64_t M = min(count[0], uint64_t(msg_room));
-    for (uint64_t m = uint64_t(blockIdx.x) * BLOCK + threadIdx.x; m < M; m += uint64_t(gridDim.x) * BLOCK)
-        valid[m] = msgs[m].len;
-}
-
-__global__ __launch_bounds__(BLOCK) void k_utf8_scan(const uint8_t* __restrict__ msg, uint64_t msg_cap,
-                                                     const wsg_msg* __restrict__ msgs,
-                                                     const uint64_t* __restrict__ count, uint32_t msg_room,
-                                                     uint32_t which, unsigned long long* __restrict__ valid)
-{
-    const uint32_t M = uint32_t(min(count[0], uint64_t(msg_room)));
-    const uint64_t bound = min(msg_cap, count[1]);
-    if (M == 0)
-        return;
-    const uint32_t lane = threadIdx.x & 63;
-    constexpr uint64_t WAVE_BYTES = 64 * CHUNK;
-    const uint64_t stride = uint64_t(gridDim.x) * BLOCK * CHUNK;
-    // (wave-uniform loop: every lane of a wave takes part in the shuffles)
-    for (uint64_t wb = (uint64_t(blockIdx.x) * (BLOCK / 64) + wave_id()) * WAVE_BYTES; wb < bound; wb += stride) {
-        const uint64_t p = wb + uint64_t(lane) * CHUNK;
-        v4u c{0, 0, 0, 0};
-        if (p < bound)
-            c = bound - p >= CHUNK ? ld16nt(msg + p) : utf8_ld_partial(msg + p, uint32_t(bound - p));
-        const bool hot = ((c.x | c.y | c.z | c.w) & 0x80808080u) != 0;   // a bad position is never an ASCII byte
-        if (__ballot(hot) == 0)
-            continue;
-        uint32_t pre = uint32_t(__shfl_up(c.w, 1, 64)), post = uint32_t(__shfl_down(c.x, 1, 64));
-        if (lane == 0)
-            pre = wb ? *reinterpret_cast<const uint32_t*>(msg + wb - 4) : 0u;
-        if (lane == 63) {
-            const uint64_t q = p + CHUNK;
-            post = 0;
-            if (q < bound)
-                post = bound - q >= 4 ? *reinterpret_cast<const uint32_t*>(msg + q)
-                                      : utf8_ld_partial(msg + q, uint32_t(bound - q)).x;
-        }
-        // the records the wave's bytes [wb, wb + WAVE_BYTES) can lie in
-        const uint32_t mlo = uni(utf8_first_beyond_wave(msgs, 0, M, wb));
-        if (mlo >= M)
-            return;   // no message ends beyond wb: nor beyond any later pass
-        const uint32_t mhi = uni(utf8_first_beyond_wave(msgs, mlo, M, wb + (WAVE_BYTES - 1)));
-        if (!hot)
-            continue;
-        uint64_t pos = p;
-        uint32_t m = mlo;
-#pragma unroll 1
-        while (pos - p < CHUNK) {
-            m = utf8_first_beyond(msgs, m, mhi, pos);
-            if (m >= M)
-                break;
-            const Utf8Rec r = utf8_rec(msgs, m, which);
-            if (r.end <= pos || r.off >= p + CHUNK)
-                break;   // (the first: a table whose ends are not sorted)
-            if (r.selected && utf8_inside(r, bound)) {
-                const int lo = r.off >= p ? int(r.off - p) : p - r.off >= 4 ? -4 : -int(p - r.off);
-                const int hi = r.end - p >= 20 ? 20 : int(r.end - p);
-                const uint32_t bad = utf8_chunk_bad(pre, c, post, lo, hi);
-                if (bad)
-                    atomicMin(valid + m, static_cast<unsigned long long>(p + uint32_t(__builtin_ctz(bad)) - r.off));
-            }
-            pos = r.end;
-        }
-    }
-}
-
-// One lane per record (grid-stride), behind the scan: the checked messages
-// with d_valid[m] < len (an unchecked one holds len), the lowest such m, the
-// messages checked and their bytes into result[0..4) (seeded by k_utf8_init),
-// one atomic of each per wave that has something to add.
-__global__ __launch_bounds__(BLOCK) void k_utf8_count(const wsg_msg* __restrict__ msgs,
-                                                      const uint64_t* __restrict__ count, uint32_t msg_room,
-                                                      uint64_t msg_cap, uint32_t which,
-                                                      const uint64_t* __restrict__ valid,
-                                                      unsigned long long* __restrict__ result)
-{
-    const uint64_t M = min(count[0], uint64_t(msg_room));
-    const uint64_t bound = min(msg_cap, count[1]);
-    uint64_t invalid = 0, lowest = UINT64_MAX, checked = 0, bytes = 0;
-    for (uint64_t m = uint64_t(blockIdx.x) * BLOCK + threadIdx.x; m < M; m += uint64_t(gridDim.x) * BLOCK) {
-        const Utf8Rec r = utf8_rec(msgs, uint32_t(m), which);
-        if (r.selected && utf8_inside(r, bound)) {
-            checked += 1;
-            bytes += r.len;
-        }
-        if (valid[m] < r.len) {
-            invalid += 1;
-            lowest = min(lowest, m);
-        }
-    }
-    invalid = wave_sum(invalid);
-    lowest = wave_min(lowest);
-    checked = wave_sum(checked);
-    bytes = wave_sum(bytes);
-    if ((threadIdx.x & 63) != 0)
-        return;
-    if (invalid) {
-        atomicAdd(result, static_cast<unsigned long long>(invalid));
-        atomicMin(result + 1, static_cast<unsigned long long>(lowest));
-    }
-    if (checked) {
-        atomicAdd(result + 2, static_cast<unsigned long long>(checked));
-        atomicAdd(result + 3, static_cast<unsigned long long>(bytes));
-    }
-}
-
-hipError_t launch_utf8_init(hipStream_t s, int grid, const wsg_msg* msgs, const uint64_t* count, uint32_t msg_room,
-                            uint64_t* valid, uint64_t* result)
-{
-    k_utf8_init<<<grid, BLOCK, 0, s>>>(msgs, count, msg_room, valid, result);
-    return hipGetLastError();
-}
-
-hipError_t launch_utf8_scan(hipStream_t s, int grid, const uint8_t* msg, uint64_t msg_cap, const wsg_msg* msgs,
-                            const uint64_t* count, uint32_t msg_room, uint32_t which, uint64_t* valid)
-{
-    k_utf8_scan<<<grid, BLOCK, 0, s>>>(msg, msg_cap, msgs, count, msg_room, which,
-                                       reinterpret_cast<unsigned long long*>(valid));
-    return hipGetLastError();
-}
-
-hipError_t launch_utf8_count(hipStream_t s, int grid, const wsg_msg* msgs, const uint64_t* count, uint32_t msg_room,
-                             uint64_t msg_cap, uint32_t which, const uint64_t* valid, uint64_t* result)
-{
-    k_utf8_count<<<grid, BLOCK, 0, s>>>(msgs, count, msg_room, msg_cap, which, valid,
-                                        reinterpret_cast<unsigned long long*>(result));
     return hipGetLastError();
 }
 

@@ -1,0 +1,695 @@
+// wsg_messages.hip — message assembly and replies on the device
+// (wsg_decode_messages, wsg_reply_messages): the plan kernels, k_msg_gather
+// and their launchers.
+#include "wsg_device.h"
+
+namespace wsg {
+
+// ===========================================================================
+// Message assembly: wsg_decode_messages
+// ===========================================================================
+//
+// The second half of PrepareReceiveFrame (ws.cpp:399-452) over a batch whose
+// frames are grouped into streams: every FIN frame ends a message made of the
+// unmasked payloads of its stream's frames since the previous FIN frame, and
+// the messages are packed back to back into one buffer.
+//
+// Plan pass, one lane per frame (BLOCK frames per block, block partials
+// scanned by one block in between):
+//   k_msg_scan_local   header parse (d_info, error latch), the frame's stream,
+//                      and three block-local scans: FIN frames before i (sum),
+//                      last frame <= i that heads a stream or names an opcode
+//                      (max: the sticky _ws_opcode), last FIN frame < i (max:
+//                      where i's message began)
+//   k_msg_scan_blocks  the three over the block partials; d_count[0]
+//   k_msg_bytes_local  a frame is delivered when its stream has a FIN frame
+//                      at or after it; block-local sums of delivered bytes
+//                      (the frame's offset in d_msg) and of pieces
+//   k_msg_bytes_blocks those over the block partials; d_count[1]; WSG_ENOMEM
+//   k_msg_finalize     FIN lanes write their wsg_msg; the gather's piece records
+//   k_msg_state        one lane per stream: consumed, _ws_opcode
+// Gather pass (k_msg_gather), the mirror of k_encode_mask: a piece is at most
+// PIECE bytes of ONE frame's payload cut at absolute 16-byte chunks of the
+// DESTINATION (rows on 128-byte lines), one wave per piece, so the key, the
+// key phase (byte index in the frame's payload mod 4) and the source shift
+// are uniform over it.  Full chunks: one aligned 16-B nontemporal load per
+// lane, the second block of the 32-byte window taken from the next lane's
+// registers, v_alignbyte funnel, XOR, 16-B nontemporal store.  The two chunks a frame shares with its
+// neighbours in d_msg: each frame stores only its own bytes (neighbours run
+// in other waves).
+
+// k_msg_gather's source loads (tools/msgbench.py, one box, C2 / C3 in
+// fragments, us): a chunk's second 16-B block is the next lane's first, so
+// it comes from that lane's registers and every block is loaded once, with
+// the nontemporal hint: 90.8 / 731.  Loaded a second time instead (as
+// k_encode_mask does): 94.4 / 769 with plain first loads, 110.7 / 832 with
+// nontemporal ones (the second read then misses); shuffled but plain loads
+// 91.3 / 778.
+#ifndef WSG_MSG_SHFL
+#define WSG_MSG_SHFL 1    // the second block from the next lane's registers (0: a second load)
+#endif
+#ifndef WSG_MSG_NT_LO
+#define WSG_MSG_NT_LO 1   // nontemporal loads of a chunk's first source block
+#endif
+#ifndef WSG_MSG_NT_HI
+#define WSG_MSG_NT_HI 1   // ... and of a second block that is loaded
+#endif
+
+namespace {
+
+// Last j < ns with sf[j] <= i (0 when there is none): the stream of frame i
+// (an empty stream shares its first index with the next one, which wins).
+__device__ __forceinline__ uint32_t stream_of(const uint32_t* __restrict__ sf, uint32_t ns, uint32_t i)
+{
+    uint32_t lo = 0, hi = ns;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (sf[mid] <= i)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+// Batch-wide values of the plan's block-local scans, for k in [0, n].
+__device__ __forceinline__ uint64_t fins_before(const MsgPlan& P, uint32_t n, uint32_t k)
+{
+    return k < n ? uint64_t(P.finx[k]) + P.bfin_pre[k / BLOCK] : P.tot[0];
+}
+__device__ __forceinline__ uint32_t last_fin_before(const MsgPlan& P, uint32_t n, uint32_t k)   // + 1; 0: none
+{
+    return k < n ? max(P.qx[k], P.bq_pre[k / BLOCK]) : uint32_t(P.tot[1]);
+}
+__device__ __forceinline__ uint64_t dst_of(const MsgPlan& P, uint32_t k)   // k < n
+{
+    return P.dst[k] + P.bbytes_pre[k / BLOCK];
+}
+__device__ __forceinline__ uint64_t pieces_before(const MsgPlan& P, uint32_t n, uint32_t k)
+{
+    return k < n ? uint64_t(P.pstart[k]) + P.bpc_pre[k / BLOCK] : P.tot[3];
+}
+// _ws_opcode after frame i of stream j (ws.cpp:326): the last non-zero
+// opcode of the stream up to i, else the stream's seed.
+__device__ __forceinline__ uint32_t sticky_opcode(const MsgPlan& P, const wsg_recv_info* __restrict__ info,
+                                                  const wsg_stream_state* state, uint32_t i, uint32_t j)
+{
+    const uint32_t pv = max(P.pinc[i], P.bp_pre[i / BLOCK]);
+    const uint32_t op = pv ? info[pv - 1].opcode : 0u;
+    return op ? op : state[j].opcode;
+}
+
+__device__ __forceinline__ uint64_t msg_pieces_of(uint64_t bytes)
+{
+    return bytes ? (bytes + PIECE_ALIGN - 1 + PIECE - 1) / PIECE : 0;
+}
+
+__device__ __forceinline__ void put_piece(MsgPiece* p, uint64_t poff, uint64_t d0, uint64_t len, uint32_t key,
+                                          uint32_t k)
+{
+    static_assert(sizeof(MsgPiece) == 32 && offsetof(MsgPiece, len) == 16 && offsetof(MsgPiece, k) == 28, "MsgPiece");
+    v4u* w = reinterpret_cast<v4u*>(p);
+    w[0] = v4u{uint32_t(poff), uint32_t(poff >> 32), uint32_t(d0), uint32_t(d0 >> 32)};
+    w[1] = v4u{uint32_t(len), uint32_t(len >> 32), key, k};
+}
+
+// pieces[t] for t in [lo, hi) of every lane's frame (fill_tiles_wave's
+// scheme: a frame of many pieces is written by the whole wave).
+__device__ __forceinline__ void fill_pieces_wave(MsgPiece* pieces, uint64_t lo, uint64_t hi, uint64_t poff,
+                                                 uint64_t d0, uint64_t len, uint32_t key)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    constexpr uint64_t kShort = 4;   // ranges up to this many pieces: the lane stores its own
+    if (hi > lo && hi - lo <= kShort)
+        for (uint64_t t = lo; t < hi; ++t)
+            put_piece(pieces + t, poff, d0, len, key, uint32_t(t - lo));
+    uint64_t pending = __ballot(hi > lo + kShort);
+    while (pending) {
+        const int j = __builtin_ctzll(pending);
+        pending &= pending - 1;
+        const uint64_t a = lane_bcast(lo, j), b = lane_bcast(hi, j);
+        const uint64_t pj = lane_bcast(poff, j), dj = lane_bcast(d0, j), lj = lane_bcast(len, j);
+        const uint32_t kj = __builtin_amdgcn_readlane(key, j);
+        for (uint64_t t = a + lane; t < b; t += 64)
+            put_piece(pieces + t, pj, dj, lj, kj, uint32_t(t - a));
+    }
+}
+
+
+// The message that FIN frame i ends (ws.cpp:411-452), as the wsg_msg fields.
+__device__ __forceinline__ MsgRec msg_at_fin(const uint8_t* __restrict__ wire, const wsg_recv_info* __restrict__ info,
+                                             uint32_t n, const uint32_t* __restrict__ sf,
+                                             const wsg_stream_state* __restrict__ state, const MsgPlan& P, uint32_t i,
+                                             uint64_t frame_len)
+{
+    const uint32_t j = P.sidx[i];
+    const uint32_t ff = min(max(last_fin_before(P, n, i), sf[j]), i);   // the message's first frame
+    const uint64_t base = dst_of(P, ff), end = dst_of(P, i) + frame_len;
+    const uint32_t op = sticky_opcode(P, info, state, i, j);
+    uint64_t off = base, len = end - base;
+    uint32_t kind = 0;
+    int32_t status = 0;
+    if (op == WSG_TEXT || op == WSG_BINARY) {
+        kind = WSG_CB_RECEIVED;
+    } else if (op == WSG_PING) {
+        kind = WSG_CB_PING;
+    } else if (op == WSG_PONG) {
+        kind = WSG_CB_PONG;
+    } else if (op == WSG_CLOSE) {
+        kind = WSG_CB_CLOSE;
+        status = 1000;
+        if (len >= 2) {   // ws.cpp:435-439: the buffer's first two bytes, wherever their frames are
+            uint32_t sb[2];
+            for (uint32_t t = 0; t < 2; ++t) {
+                const uint64_t x = base + t;
+                uint32_t a = ff, b = i + 1;   // last k in [ff, i] with dst_of(k) <= x holds byte x
+                while (b - a > 1) {
+                    const uint32_t mid = a + (b - a) / 2;
+                    if (dst_of(P, mid) <= x)
+                        a = mid;
+                    else
+                        b = mid;
+                }
+                const uint64_t o = x - dst_of(P, a);
+                // (o < len unless stream_first is malformed: never a read past the payload)
+                sb[t] = o < info[a].len ? uint32_t(wire[info[a].payload_off + o]) ^ key_byte(info[a].key, o) : 0u;
+            }
+            status = int32_t((sb[0] << 8) | sb[1]);
+            off += 2;
+            len -= 2;
+        }
+    }
+    return MsgRec{off, len, j, ff, kind, op, status};
+}
+
+} // namespace
+
+__global__ __launch_bounds__(BLOCK) void k_msg_scan_local(const uint8_t* __restrict__ wire, uint64_t wire_len,
+                                                          const uint64_t* __restrict__ fs, uint32_t n,
+                                                          const uint32_t* __restrict__ sf, uint32_t ns,
+                                                          wsg_recv_info* __restrict__ info, MsgPlan P,
+                                                          unsigned long long* err)
+{
+    const uint64_t i64 = uint64_t(blockIdx.x) * BLOCK + threadIdx.x;
+    const uint32_t i = uint32_t(i64);
+    uint32_t fin = 0, pv = 0;
+    if (i64 < n) {
+        wsg_recv_info r;
+        const int e = frame_parse(wire, wire_len, fs[i], i + 1 < n ? fs[i + 1] : wire_len, r);
+        if (e != 0)
+            latch(err, i, e);
+        store_info(info + i, r);
+        const uint32_t j = stream_of(sf, ns, i);
+        P.sidx[i] = j;
+        fin = r.fin;
+        pv = (r.opcode != 0 || sf[j] == i) ? i + 1 : 0;
+    }
+    uint32_t tf, tp, tq;
+    const uint32_t ef = block_scan_ex(fin, OpAdd{}, &tf);
+    const uint32_t ep = block_scan_ex(pv, OpMax{}, &tp);
+    const uint32_t eq = block_scan_ex(fin ? i + 1 : 0u, OpMax{}, &tq);
+    if (i64 < n) {
+        P.finx[i] = ef;
+        P.pinc[i] = max(ep, pv);
+        P.qx[i] = eq;
+    }
+    if (threadIdx.x == 0) {
+        P.bfin[blockIdx.x] = tf;
+        P.bp[blockIdx.x] = tp;
+        P.bq[blockIdx.x] = tq;
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_msg_scan_blocks(MsgPlan P, uint32_t nb, uint64_t* __restrict__ count)
+{
+    const uint32_t cf = scan_partials(P.bfin, P.bfin_pre, nb, OpAdd{});
+    scan_partials(P.bp, P.bp_pre, nb, OpMax{});
+    const uint32_t cq = scan_partials(P.bq, P.bq_pre, nb, OpMax{});
+    if (threadIdx.x == 0) {
+        P.tot[0] = cf;
+        P.tot[1] = cq;
+        count[0] = cf;
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_msg_bytes_local(const wsg_recv_info* __restrict__ info, uint32_t n,
+                                                           const uint32_t* __restrict__ sf, MsgPlan P)
+{
+    const uint64_t i64 = uint64_t(blockIdx.x) * BLOCK + threadIdx.x;
+    const uint32_t i = uint32_t(i64);
+    uint64_t dl = 0;
+    if (i64 < n) {
+        const uint32_t end = min(sf[P.sidx[i] + 1], n);
+        if (fins_before(P, n, end) > fins_before(P, n, i))   // a FIN frame in [i, end): not in the tail
+            dl = info[i].len;
+    }
+    uint64_t tb, tp;
+    const uint64_t eb = block_scan_ex(dl, OpAdd{}, &tb);
+    const uint64_t ep = block_scan_ex(msg_pieces_of(dl), OpAdd{}, &tp);
+    if (i64 < n) {
+        P.dst[i] = eb;
+        P.pstart[i] = uint32_t(ep);
+    }
+    if (threadIdx.x == 0) {
+        P.bbytes[blockIdx.x] = tb;
+        P.bpc[blockIdx.x] = tp;
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_msg_bytes_blocks(MsgPlan P, uint32_t nb, uint32_t n, uint64_t msg_cap,
+                                                            uint64_t* __restrict__ count, unsigned long long* err)
+{
+    const uint64_t cb = scan_partials(P.bbytes, P.bbytes_pre, nb, OpAdd{});
+    const uint64_t cp = scan_partials(P.bpc, P.bpc_pre, nb, OpAdd{});
+    if (threadIdx.x == 0) {
+        P.tot[2] = cb;
+        P.tot[3] = cp;
+        count[1] = cb;
+        if (cb > msg_cap)   // behind every frame error: the latch keeps the smallest
+            latch(err, n, WSG_ENOMEM);
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_msg_finalize(const uint8_t* __restrict__ wire,
+                                                        const wsg_recv_info* __restrict__ info, uint32_t n,
+                                                        const uint32_t* __restrict__ sf,
+                                                        const wsg_stream_state* __restrict__ state, MsgPlan P,
+                                                        wsg_msg* __restrict__ msgs,
+                                                        MsgPiece* __restrict__ pieces, uint64_t pieces_cap)
+{
+    if (uint64_t(blockIdx.x) * BLOCK + (threadIdx.x & ~63u) >= n)
+        return;   // whole wave past the last frame
+    const uint64_t i64 = uint64_t(blockIdx.x) * BLOCK + threadIdx.x;
+    const uint32_t i = uint32_t(i64);
+    uint64_t lo = 0, hi = 0, poff = 0, d0 = 0, plen = 0;
+    uint32_t key = 0;
+    if (i64 < n) {
+        piece_range(pieces_before(P, n, i), pieces_before(P, n, i + 1), pieces_cap, lo, hi);
+        const wsg_recv_info r = info[i];
+        poff = r.payload_off;
+        plen = r.len;
+        key = r.key;
+        d0 = dst_of(P, i);
+        if (r.fin)
+            put_msg(msgs + fins_before(P, n, i), msg_at_fin(wire, info, n, sf, state, P, i, r.len), i);
+    }
+    fill_pieces_wave(pieces, lo, hi, poff, d0, plen, key);
+}
+
+__global__ __launch_bounds__(BLOCK) void k_msg_state(const wsg_recv_info* __restrict__ info, uint32_t n,
+                                                     const uint32_t* __restrict__ sf, uint32_t ns,
+                                                     wsg_stream_state* state, MsgPlan P)
+{
+    static_assert(sizeof(wsg_stream_state) == 8 && offsetof(wsg_stream_state, opcode) == 4, "wsg_stream_state layout");
+    const uint64_t j64 = uint64_t(blockIdx.x) * BLOCK + threadIdx.x;
+    if (j64 >= ns)
+        return;
+    const uint32_t j = uint32_t(j64);
+    const uint32_t start = min(sf[j], n), end = max(min(sf[j + 1], n), start);
+    uint32_t consumed = 0, op = state[j].opcode;
+    if (fins_before(P, n, end) > fins_before(P, n, start)) {
+        const uint32_t last = last_fin_before(P, n, end);   // + 1: in (start, end]
+        if (last > start && last <= end) {
+            consumed = last - start;
+            op = sticky_opcode(P, info, state, last - 1, j);
+        }
+    }
+    *reinterpret_cast<uint64_t*>(state + j) = uint64_t(consumed) | (uint64_t(op & 0xFFu) << 32);
+}
+
+// ---- replies (wsg_reply_messages) -------------------------------------------
+// The plan above up to k_msg_bytes_blocks, then, one lane per frame again:
+//   k_reply_local     FIN lanes write their wsg_msg and size the reply frame
+//                     (send_geom); block-local sums of the reply sizes.  The
+//                     sum over the FIN frames before frame i is the reply
+//                     offset of the message frame i belongs to, FIN or not.
+//   k_reply_blocks    those over the block partials; d_count[2..3]; the
+//                     capacity latch; the gather's totals (P.rtot)
+//   k_reply_finalize  FIN lanes: d_reply_off, header and status prefix (byte
+//                     stores, frame_head's bytes); every lane: its frame's
+//                     piece records with the reply wire as destination and
+//                     the receive key XOR the send key at the destination's
+//                     phase; a lane per stream: d_stream_reply
+// and k_msg_gather over those records: every payload byte is read once from
+// the received wire and written once, re-keyed, into its reply frame.
+
+namespace {
+
+// What message r is answered with: the first header byte (0: nothing), the
+// data length and the status of the PrepareSendFrame call.
+struct ReplyOf {
+    uint8_t op;
+    uint64_t len;
+    int32_t status;
+};
+
+__device__ __forceinline__ ReplyOf reply_of(const ReplyRule& rule, uint32_t kind, uint32_t opcode, uint64_t len,
+                                            int32_t status)
+{
+    const uint8_t v = kind >= 1 && kind <= 4 ? rule.op[kind] : uint8_t(0);
+    ReplyOf r;
+    r.op = v == WSG_REPLY_SAME ? uint8_t(WSG_FIN | opcode) : v;
+    r.len = kind == WSG_CB_CLOSE ? 0 : len;   // a close reply carries the status and no data
+    r.status = kind == WSG_CB_CLOSE ? status : 0;
+    return r;
+}
+
+__device__ __forceinline__ uint64_t reply_size(const ReplyRule& rule, const ReplyOf& r)
+{
+    if (!r.op)
+        return 0;
+    const SendGeom g = send_geom(r.op, rule.mask != 0, r.len, r.status);
+    return g.hdr + g.body;
+}
+
+// Reply bytes of the FIN frames before frame k, for k in [0, n].
+__device__ __forceinline__ uint64_t reply_before(const MsgPlan& P, uint32_t n, uint32_t k)
+{
+    return k < n ? P.rex[k] + P.brep_pre[k / BLOCK] : P.rtot[2];
+}
+
+} // namespace
+
+__global__ __launch_bounds__(BLOCK) void k_reply_local(const uint8_t* __restrict__ wire,
+                                                       const wsg_recv_info* __restrict__ info, uint32_t n,
+                                                       const uint32_t* __restrict__ sf,
+                                                       const wsg_stream_state* __restrict__ state, MsgPlan P,
+                                                       ReplyRule rule, wsg_msg* __restrict__ msgs)
+{
+    const uint64_t i64 = uint64_t(blockIdx.x) * BLOCK + threadIdx.x;
+    const uint32_t i = uint32_t(i64);
+    uint64_t size = 0;
+    if (i64 < n && info[i].fin) {
+        const MsgRec m = msg_at_fin(wire, info, n, sf, state, P, i, info[i].len);
+        put_msg(msgs + fins_before(P, n, i), m, i);
+        size = reply_size(rule, reply_of(rule, m.kind, m.op, m.len, m.status));
+    }
+    uint64_t tb, tn;
+    const uint64_t eb = block_scan_ex(size, OpAdd{}, &tb);
+    block_scan_ex(uint64_t(size != 0), OpAdd{}, &tn);
+    if (i64 < n)
+        P.rex[i] = eb;
+    if (threadIdx.x == 0) {
+        P.brep[blockIdx.x] = tb;
+        P.brn[blockIdx.x] = tn;
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_reply_blocks(MsgPlan P, uint32_t nb, uint32_t n, uint64_t reply_cap,
+                                                        uint64_t* __restrict__ count, unsigned long long* err)
+{
+    const uint64_t cb = scan_partials(P.brep, P.brep_pre, nb, OpAdd{});
+    const uint64_t cn = scan_partials<uint64_t>(P.brn, nullptr, nb, OpAdd{});
+    if (threadIdx.x == 0) {
+        P.rtot[2] = cb;         // k_msg_gather's view of the totals: bytes against the capacity,
+        P.rtot[3] = P.tot[3];   // and the piece count
+        count[2] = cb;
+        count[3] = cn;
+        if (cb > reply_cap)   // behind every frame error: the latch keeps the smallest
+            latch(err, n, WSG_ENOMEM);
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_reply_finalize(const wsg_recv_info* __restrict__ info, uint32_t n,
+                                                          const uint32_t* __restrict__ sf, uint32_t ns, MsgPlan P,
+                                                          ReplyRule rule, const uint32_t* __restrict__ send_key,
+                                                          const wsg_msg* __restrict__ msgs,
+                                                          uint8_t* __restrict__ reply, uint64_t reply_cap,
+                                                          uint64_t* __restrict__ reply_off,
+                                                          uint64_t* __restrict__ stream_reply,
+                                                          MsgPiece* __restrict__ pieces, uint64_t pieces_cap)
+{
+    const uint64_t i64 = uint64_t(blockIdx.x) * BLOCK + threadIdx.x;
+    const uint32_t i = uint32_t(i64);
+    const uint64_t total = P.rtot[2], nmsg = P.tot[0];
+    // connection j's replies start where its first message's does
+    for (uint64_t j = i64; j <= ns; j += uint64_t(gridDim.x) * BLOCK)
+        stream_reply[j] = reply_before(P, n, min(sf[j], n));
+    if (i64 == 0)
+        reply_off[nmsg] = total;
+    uint64_t lo = 0, hi = 0, poff = 0, d0 = 0, plen = 0;
+    uint32_t key = 0;
+    if (i64 < n) {
+        piece_range(pieces_before(P, n, i), pieces_before(P, n, i + 1), pieces_cap, lo, hi);
+        const wsg_recv_info r = info[i];
+        const uint64_t m = fins_before(P, n, i);
+        if ((r.fin || hi > lo) && m < nmsg) {   // frame i belongs to message m
+            const MsgRec mr = get_msg(msgs + m);
+            const ReplyOf a = reply_of(rule, mr.kind, mr.op, mr.len, mr.status);
+            const uint64_t at = reply_before(P, n, i);
+            const uint32_t skey = send_key ? send_key[mr.stream] : 0u;
+            if (r.fin)
+                reply_off[m] = at;
+            if (a.op) {
+                const FrameRec R = make_rec(at, nullptr, a.len, skey, a.status, a.op, rule.mask != 0);
+                if (r.fin && total <= reply_cap) {
+                    const v4u h = frame_head(R);
+                    for (uint32_t t = 0; t < R.hdr + R.prefix; ++t)
+                        reply[at + t] = uint8_t(lane_byte(h, t));
+                }
+                // data byte dst_of(i) - mr.off of the message: c bytes into the reply's payload
+                // (inside the message unless stream_first is malformed: never a store outside the frame)
+                const uint64_t rel = dst_of(P, i) - mr.off;
+                if (a.len && dst_of(P, i) >= mr.off && rel <= a.len && r.len <= a.len - rel) {
+                    const uint64_t c = R.prefix + rel;
+                    poff = r.payload_off;
+                    plen = r.len;
+                    d0 = R.pw + c;
+                    key = r.key ^ key_rot(skey, uint32_t(c));
+                }
+            }
+        }
+    }
+    // (a frame whose message gets no data keeps d0 = plen = 0: its pieces are empty)
+    fill_pieces_wave(pieces, lo, hi, poff, d0, plen, key);
+}
+
+__global__ __launch_bounds__(BLOCK) void k_msg_gather(const uint8_t* __restrict__ wire,
+                                                      const uint64_t* __restrict__ tot,
+                                                      const MsgPiece* __restrict__ piece_recs, uint64_t pieces_cap,
+                                                      uint8_t* __restrict__ msg, uint64_t msg_cap)
+{
+    const uint64_t waves = uint64_t(gridDim.x) * (BLOCK / 64);
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t q0 = uint64_t(blockIdx.x) * (BLOCK / 64) + wave_id();
+    if (tot[2] > msg_cap)
+        return;   // WSG_ENOMEM latched by k_msg_bytes_blocks: no byte of msg
+    const uint64_t pieces = min(tot[3], pieces_cap);
+    for (uint64_t q = q0; q < pieces; q += waves) {
+        // the record as dwords (wave-uniform: one scalar load, as load_desc)
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(piece_recs + q);
+        const uint64_t poff = uint64_t(w[0]) | (uint64_t(w[1]) << 32);
+        const uint64_t d0 = uint64_t(w[2]) | (uint64_t(w[3]) << 32);
+        const uint64_t len = uint64_t(w[4]) | (uint64_t(w[5]) << 32);
+        const uint32_t key = w[6];
+        const uint64_t k = w[7];
+        const uint64_t end = d0 + len;
+        const uint64_t lo = (d0 & ~(PIECE_ALIGN - 1)) + k * PIECE;
+        if (lo >= end || end > msg_cap)
+            continue;   // piece counts are an upper bound
+        const uint64_t hi = min(lo + PIECE, end);
+        // source of msg byte p: src + (p - d0), as pointer arithmetic on the
+        // wire argument (global_* loads)
+        const uint8_t* src = wire + poff;
+        const uint32_t s = uint32_t((reinterpret_cast<uintptr_t>(src) + (lo - d0)) & 15u);
+        const uint32_t kw = key_rot(key, uint32_t(lo - d0));   // phase: byte index in the payload (mod 4 also when lo < d0)
+        v4u a[EU], b[EU];
+        uint32_t full = 0;
+#pragma unroll
+        for (int u = 0; u < EU; ++u) {
+            const uint64_t p = lo + (uint64_t(u) * 64 + lane) * CHUNK;
+            const bool f = p < hi && p >= d0 && p + CHUNK <= end;
+            full |= uint32_t(f) << u;
+            const uint8_t* a0 = src + (int64_t(p - d0) - int64_t(s));
+            a[u] = f ? (WSG_MSG_NT_LO ? ld16nt(a0) : ld16(a0)) : v4u{0, 0, 0, 0};
+        }
+#if !WSG_MSG_SHFL
+#pragma unroll
+        for (int u = 0; u < EU; ++u) {
+            const uint64_t p = lo + (uint64_t(u) * 64 + lane) * CHUNK;
+            const uint8_t* a0 = src + (int64_t(p - d0) - int64_t(s));
+            b[u] = ((full >> u) & 1u) && s ? (WSG_MSG_NT_HI ? ld16nt(a0 + CHUNK) : ld16(a0 + CHUNK)) : v4u{0, 0, 0, 0};
+        }
+#else
+        // bit u: the lane after this one in the piece (lane 0 of the next row
+        // for lane 63) loaded the block after a[u] as its own first block
+        const uint32_t nfull = lane == 63 ? uint32_t(__builtin_amdgcn_readlane(full, 0)) >> 1
+                                          : uint32_t(__shfl_down(full, 1, 64));
+#pragma unroll
+        for (int u = 0; u < EU; ++u) {
+            const uint64_t p = lo + (uint64_t(u) * 64 + lane) * CHUNK;
+            const uint8_t* a0 = src + (int64_t(p - d0) - int64_t(s));
+            b[u] = ((full >> u) & 1u) && s && !((nfull >> u) & 1u)
+                       ? (WSG_MSG_NT_HI ? ld16nt(a0 + CHUNK) : ld16(a0 + CHUNK))
+                       : v4u{0, 0, 0, 0};
+        }
+        if (s) {
+#pragma unroll
+            for (int u = 0; u < EU; ++u) {
+                v4u nx;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const uint32_t first = u + 1 < EU ? uint32_t(__builtin_amdgcn_readlane(a[u + 1 < EU ? u + 1 : u][c], 0)) : 0u;
+                    const uint32_t down = uint32_t(__shfl_down(a[u][c], 1, 64));
+                    nx[c] = lane == 63 ? first : down;
+                }
+                if ((nfull >> u) & 1u)
+                    b[u] = nx;
+            }
+        }
+#endif
+        // the full chunks first, in a straight line: with the edge chunks'
+        // loads and byte stores between them every store waited for the one
+        // before it (stores count in vmcnt on gfx9)
+#pragma unroll
+        for (int u = 0; u < EU; ++u)
+            a[u] = (s ? funnel(a[u], b[u], s) : a[u]) ^ kw;
+#pragma unroll
+        for (int u = 0; u < EU; ++u) {
+            const uint64_t p = lo + (uint64_t(u) * 64 + lane) * CHUNK;
+            if ((full >> u) & 1u)
+                st16nt(msg + p, a[u]);
+        }
+        // the (at most two) chunks shared with a neighbour frame: this
+        // frame's bytes only; wave-uniform test, most pieces have none
+        const bool head_edge = lo <= d0 && (d0 & (CHUNK - 1)) != 0;
+        const bool tail_edge = hi == end && (end & (CHUNK - 1)) != 0;
+        if (!head_edge && !tail_edge)
+            continue;
+#pragma unroll 1
+        for (uint32_t u = 0; u < uint32_t(EU); ++u) {
+            const uint64_t p = lo + (uint64_t(u) * 64 + lane) * CHUNK;
+            if (((full >> u) & 1u) || p >= hi || p + CHUNK <= d0)
+                continue;
+            const v4u v = fan_window(src, len, int64_t(p) - int64_t(d0)) ^ kw;
+            const uint32_t o_lo = p < d0 ? uint32_t(d0 - p) : 0u;
+            const uint32_t o_hi = end - p < CHUNK ? uint32_t(end - p) : uint32_t(CHUNK);
+            uint32_t* m32 = reinterpret_cast<uint32_t*>(msg + p);
+#pragma unroll
+            for (uint32_t c = 0; c < 4; ++c) {
+                const uint32_t b0 = 4 * c, b1 = b0 + 4;
+                if (b0 >= o_lo && b1 <= o_hi) {
+                    m32[c] = v[c];
+                } else {
+                    for (uint32_t t = max(b0, o_lo); t < min(b1, o_hi); ++t)
+                        msg[p + t] = uint8_t(v[c] >> (8 * (t - b0)));
+                }
+            }
+        }
+    }
+}
+
+uint64_t msg_plan_layout(uint8_t* base, uint32_t n, MsgPlan* plan)
+{
+    const uint64_t nb = (uint64_t(n) + BLOCK - 1) / BLOCK;
+    Carve c{base, 16};
+    MsgPlan P;
+    P.dst = c.take<uint64_t>(n);
+    P.bbytes = c.take<uint64_t>(nb);
+    P.bbytes_pre = c.take<uint64_t>(nb);
+    P.bpc = c.take<uint64_t>(nb);
+    P.bpc_pre = c.take<uint64_t>(nb);
+    P.tot = c.take<uint64_t>(4);
+    P.finx = c.take<uint32_t>(n);
+    P.pinc = c.take<uint32_t>(n);
+    P.qx = c.take<uint32_t>(n);
+    P.sidx = c.take<uint32_t>(n);
+    P.pstart = c.take<uint32_t>(n);
+    P.bfin = c.take<uint32_t>(nb);
+    P.bfin_pre = c.take<uint32_t>(nb);
+    P.bp = c.take<uint32_t>(nb);
+    P.bp_pre = c.take<uint32_t>(nb);
+    P.bq = c.take<uint32_t>(nb);
+    P.bq_pre = c.take<uint32_t>(nb);
+    P.rex = c.take<uint64_t>(n);
+    P.brep = c.take<uint64_t>(nb);
+    P.brep_pre = c.take<uint64_t>(nb);
+    P.brn = c.take<uint64_t>(nb);
+    P.rtot = c.take<uint64_t>(4);
+    if (plan)
+        *plan = P;
+    return c.at;
+}
+
+// What the two plans share: the scans up to k_msg_bytes_blocks and then
+// finish(nb), or, for no frame (no message, every stream unchanged with
+// nothing consumed), the totals and count_words of d_count zeroed; k_msg_state
+// behind either.
+template <class Finish>
+static hipError_t launch_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
+                              const uint32_t* stream_first, uint32_t n_streams, wsg_stream_state* state,
+                              uint64_t msg_cap, uint64_t* count, uint32_t count_words, wsg_recv_info* info,
+                              const MsgPlan& plan, unsigned long long* err, Finish finish)
+{
+    const uint32_t nb = uint32_t((uint64_t(n) + BLOCK - 1) / BLOCK);
+    if (n == 0) {
+        if (hipError_t e = hipMemsetAsync(plan.tot, 0, 4 * sizeof(uint64_t), s); e != hipSuccess)
+            return e;
+        if (hipError_t e = hipMemsetAsync(count, 0, count_words * sizeof(uint64_t), s); e != hipSuccess)
+            return e;
+    } else {
+        k_msg_scan_local<<<nb, BLOCK, 0, s>>>(wire, wire_len, fs, n, stream_first, n_streams, info, plan, err);
+        k_msg_scan_blocks<<<1, BLOCK, 0, s>>>(plan, nb, count);
+        k_msg_bytes_local<<<nb, BLOCK, 0, s>>>(info, n, stream_first, plan);
+        k_msg_bytes_blocks<<<1, BLOCK, 0, s>>>(plan, nb, n, msg_cap, count, err);
+        finish(nb);
+    }
+    if (n_streams)
+        k_msg_state<<<(n_streams + BLOCK - 1) / BLOCK, BLOCK, 0, s>>>(info, n, stream_first, n_streams, state, plan);
+    return hipGetLastError();
+}
+
+hipError_t launch_msg_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
+                           const uint32_t* stream_first, uint32_t n_streams, wsg_stream_state* state, uint64_t msg_cap,
+                           wsg_msg* msgs, uint64_t* count, wsg_recv_info* info, const MsgPlan& plan,
+                           MsgPiece* pieces, uint64_t pieces_cap, unsigned long long* err)
+{
+    return launch_plan(s, wire, wire_len, fs, n, stream_first, n_streams, state, msg_cap, count, 2, info, plan, err,
+                       [&](uint32_t nb) {
+                           k_msg_finalize<<<nb, BLOCK, 0, s>>>(wire, info, n, stream_first, state, plan, msgs, pieces,
+                                                               pieces_cap);
+                       });
+}
+
+hipError_t launch_msg_gather(hipStream_t s, int grid, const uint8_t* wire, const MsgPlan& plan,
+                             const MsgPiece* pieces, uint64_t pieces_cap, uint8_t* msg, uint64_t msg_cap)
+{
+    k_msg_gather<<<grid, BLOCK, 0, s>>>(wire, plan.tot, pieces, pieces_cap, msg, msg_cap);
+    return hipGetLastError();
+}
+
+hipError_t launch_reply_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
+                             const uint32_t* stream_first, uint32_t n_streams, wsg_stream_state* state,
+                             const ReplyRule& rule, const uint32_t* send_key, uint8_t* reply, uint64_t reply_cap,
+                             uint64_t* reply_off, uint64_t* stream_reply, wsg_msg* msgs, uint64_t* count,
+                             wsg_recv_info* info, const MsgPlan& plan, MsgPiece* pieces, uint64_t pieces_cap,
+                             unsigned long long* err)
+{
+    if (n == 0) {   // no reply either
+        if (hipError_t e = hipMemsetAsync(plan.rtot, 0, 4 * sizeof(uint64_t), s); e != hipSuccess)
+            return e;
+        if (hipError_t e = hipMemsetAsync(reply_off, 0, sizeof(uint64_t), s); e != hipSuccess)
+            return e;
+        if (hipError_t e = hipMemsetAsync(stream_reply, 0, (uint64_t(n_streams) + 1) * sizeof(uint64_t), s);
+            e != hipSuccess)
+            return e;
+    }
+    // (no d_msg: its size, d_count[1], meets no capacity)
+    return launch_plan(s, wire, wire_len, fs, n, stream_first, n_streams, state, UINT64_MAX, count, 4, info, plan, err,
+                       [&](uint32_t nb) {
+                           k_reply_local<<<nb, BLOCK, 0, s>>>(wire, info, n, stream_first, state, plan, rule, msgs);
+                           k_reply_blocks<<<1, BLOCK, 0, s>>>(plan, nb, n, reply_cap, count, err);
+                           k_reply_finalize<<<nb, BLOCK, 0, s>>>(info, n, stream_first, n_streams, plan, rule, send_key,
+                                                                 msgs, reply, reply_cap, reply_off, stream_reply,
+                                                                 pieces, pieces_cap);
+                       });
+}
+
+hipError_t launch_reply_gather(hipStream_t s, int grid, const uint8_t* wire, const MsgPlan& plan,
+                               const MsgPiece* pieces, uint64_t pieces_cap, uint8_t* reply, uint64_t reply_cap)
+{
+    k_msg_gather<<<grid, BLOCK, 0, s>>>(wire, plan.rtot, pieces, pieces_cap, reply, reply_cap);
+    return hipGetLastError();
+}
+
+} // namespace wsg

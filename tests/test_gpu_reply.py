@@ -25,6 +25,7 @@ from tests import messages_cases as mc  # noqa: E402
 from tests import reply_cases as rc  # noqa: E402
 from tests.test_gpu_async import _gate  # noqa: E402
 from tests.test_gpu_launch_shapes import _codec  # noqa: E402
+from tests.test_gpu_messages import PLAN_BLOCK, _three_pass_batch  # noqa: E402
 
 SENTINEL = 0xA5
 SLACK = 64   # bytes of d_reply past reply_cap: must stay sentinel whatever happens
@@ -341,6 +342,32 @@ def test_scans_past_one_block_and_grid_stride():
         run(c, big, rc.SAME_CLOSE_PONG, 0, keys)
     finally:
         c.close()
+
+
+def test_reply_scans_three_passes(codec):
+    """tests/test_gpu_messages.py's three-pass batch (131 716 frames: three
+    passes of 256 block partials) as replies.  Messages end in passes one and
+    three of the partials and none in pass two, so k_reply_blocks' two
+    carries, reply bytes and reply frames, come through a pass that adds
+    nothing to either, and the prefixes of pass three hold pass one's sum."""
+    batch, _ = _three_pass_batch()
+    rule, mask = rc.SAME_CLOSE_PONG, 1
+    keys = np.random.default_rng(55).integers(0, 2**32, batch.n_streams).astype(np.uint32)
+    out_o, info_o = batch.oracle_decode()
+    msgs, _, _ = layout.message_plan(info_o, batch.stream_first, None, payload=out_o)
+    reply_off, _, rcount = layout.reply_plan(msgs, rule, mask, keys, n_streams=batch.n_streams)
+    per_pass = PLAN_BLOCK * PLAN_BLOCK   # frames whose block partials one pass scans
+    assert 2 * per_pass < batch.n <= 3 * per_pass
+    ends = msgs["first_frame"].astype(np.int64) + msgs["nframes"] - 1   # the FIN frame: where the reply is counted
+    size = np.diff(reply_off.astype(np.int64))
+    in_pass = [(ends >= k * per_pass) & (ends < (k + 1) * per_pass) for k in range(3)]
+    for k in range(3):
+        print("pass", k + 1, "messages", int(in_pass[k].sum()), "reply frames", int((size[in_pass[k]] > 0).sum()),
+              "reply bytes", int(size[in_pass[k]].sum()))
+    assert not in_pass[1].any()
+    assert (size[in_pass[0]] > 0).any() and (size[in_pass[2]] > 0).any()
+    assert int(size.sum()) == int(rcount[0]) and int((size > 0).sum()) == int(rcount[1])
+    run(codec, batch, rule, mask, keys)
 
 
 # ------------------------------------------------------------------ capacity

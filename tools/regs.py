@@ -10,7 +10,11 @@ import subprocess
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "cppserver_amd", "csrc", "wsg_kernels.hip")
+
+
+def source(name):
+    with open(os.path.join(ROOT, "cppserver_amd", "csrc", name)) as f:
+        return f.read()
 
 
 def report(text, tag, kernel="_ZN3wsg8k_decode"):
@@ -40,20 +44,17 @@ def cut(text, marker):
 
 
 if __name__ == "__main__":
-    src = open(SRC).read()
+    src = source("wsg_kernels.hip")
     staged = "    // staged: payload segments in LDS"
     boundary = "        // boundary: per chunk"
     report(src, "full")
     report(cut(src, staged), "no-staged")
     report(cut(src, boundary), "no-boundary")
     report(cut(cut(src, staged), boundary), "no-staged-no-boundary")
-    report(src, "k_msg_gather", kernel="_ZN3wsg12k_msg_gather")
-    report(src, "k_msg_finalize", kernel="_ZN3wsg14k_msg_finalize")
-    report(src, "k_reply_local", kernel="_ZN3wsg13k_reply_local")
-    report(src, "k_reply_blocks", kernel="_ZN3wsg14k_reply_blocks")
-    report(src, "k_reply_finalize", kernel="_ZN3wsg16k_reply_finalize")
-    report(src, "k_frame_count", kernel="_ZN3wsg13k_frame_count")
-    report(src, "k_frame_write", kernel="_ZN3wsg13k_frame_write")
-    report(src, "k_utf8_init", kernel="_ZN3wsg11k_utf8_init")
-    report(src, "k_utf8_scan", kernel="_ZN3wsg11k_utf8_scan")
-    report(src, "k_utf8_count", kernel="_ZN3wsg12k_utf8_count")
+    for name, kernels in (("wsg_messages.hip", ("k_msg_gather", "k_msg_finalize", "k_reply_local", "k_reply_blocks",
+                                                "k_reply_finalize")),
+                          ("wsg_frames.hip", ("k_frame_count", "k_frame_write")),
+                          ("wsg_utf8.hip", ("k_utf8_init", "k_utf8_scan", "k_utf8_count"))):
+        src = source(name)
+        for k in kernels:
+            report(src, k, kernel="_ZN3wsg%d%s" % (len(k), k))

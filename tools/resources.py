@@ -1,11 +1,14 @@
 """Summarize hipcc -Rpass-analysis=kernel-resource-usage output per kernel."""
+import fileinput
+import glob
 import re
 import sys
 
-path = sys.argv[1] if len(sys.argv) > 1 else "cppserver_amd/_build/asm/resource-usage.txt"
+# `make asm` writes one file per kernel source
+paths = sys.argv[1:] or sorted(glob.glob("cppserver_amd/_build/asm/resource-usage-*.txt"))
 rows, cur = [], None
 KEYS = [("TotalSGPRs", "sgpr"), ("VGPRs", "vgpr"), ("ScratchSize", "scratch"), ("Occupancy", "occ"), ("LDS Size", "lds")]
-for line in open(path):
+for line in fileinput.input(paths) if paths else ():
     m = re.search(r"Function Name: (\S+)", line)
     if m:
         cur = {"name": re.sub(r"^_ZN3wsg\d+", "", m.group(1))[:28]}
