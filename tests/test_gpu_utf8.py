@@ -548,3 +548,111 @@ def test_graph_replay_follows_new_bytes():
             assert verify(batch)[0] > 0
     finally:
         c.close()
+
+
+# ------------------------------------------------- 11. the 1 KiB wave edges
+# A wave of k_utf8_scan owns 1 KiB of d_msg, a 16-byte chunk per lane; the 4
+# bytes on either side of a chunk come from the neighbouring lanes' registers,
+# except lane 0's `pre` and lane 63's `post`, which those lanes load themselves
+# (the `post` byte by byte where the bound cuts it).  Only a multi-byte
+# sequence on a wave edge, or a bound 1 to 3 bytes behind one, lets those
+# loads decide a verdict.
+EDGE_BASE = bytes(range(0x30, 0x60))   # 48 ASCII bytes
+EDGE_AT = 20                           # the sequence's offset in its message
+
+
+def _edge_codec(one_block):
+    if not one_block:
+        return ca.Codec(0)
+    os.environ["WSG_UTF8_BLOCKS_PER_CU"] = "1"
+    try:
+        return ca.Codec(0)
+    finally:
+        del os.environ["WSG_UTF8_BLOCKS_PER_CU"]
+
+
+def _edge_waves(one_block):
+    """The edges 1024 w looked at; with one block per CU also the first byte
+    of pass two (test_large_message_later_passes' pass size)."""
+    if not one_block:
+        return [1, 2, 5]
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    return [1, 2, 5, cus * 4096 // 1024]
+
+
+def _edge_batch(placed):
+    """One stream: in front of each (text, pos, offset) a binary message of FF
+    bytes (never checked, every lane of its waves hot) that brings the text
+    message's byte `pos` to the dense `offset`."""
+    frames, used = [], 0
+    for i, (text, pos, offset) in enumerate(placed):
+        fill = offset - pos - used
+        assert fill >= 0
+        frames += [frame(BINARY, b"\xff" * fill, key=3 + i), frame(TEXT, text, key=0x01020304 + i)]
+        used += fill + len(text)
+    return mc.Batch([frames])
+
+
+@pytest.mark.parametrize("one_block", [False, True], ids=["default", "1-block-per-cu"])
+def test_sequences_on_wave_edges(one_block):
+    """EURO and GRIN with their first byte at the dense offsets 1024 w - s,
+    s = 0..4: valid; the byte above the edge made 41 (the bad position is the
+    lead byte in lane 63, judged by the `post` that lane loaded); the bytes
+    below the edge made 41 (a stray continuation in lane 0, judged by its own
+    `pre`)."""
+    c = _edge_codec(one_block)
+    try:
+        ws = _edge_waves(one_block)
+        for seq in (uc.EURO, uc.GRIN):
+            good = EDGE_BASE[:EDGE_AT] + seq + EDGE_BASE[EDGE_AT + len(seq):]
+            for s in range(5):
+                above = bytearray(good)
+                above[EDGE_AT + s] = 0x41
+                below = bytearray(good)
+                below[EDGE_AT: EDGE_AT + min(s, len(seq))] = b"\x41" * min(s, len(seq))
+                inside = 0 < s < len(seq)                          # the edge cuts the sequence
+                for text, want in ((good, 48), (bytes(above), EDGE_AT if inside else None),
+                                   (bytes(below), EDGE_AT + s if inside else None)):
+                    batch = _edge_batch([(text, EDGE_AT, 1024 * w - s) for w in ws])
+                    msgs, valid, result = run(c, batch, ca.UTF8_TEXT)
+                    assert [int(o) + EDGE_AT + s for o in msgs["off"][1::2]] == [1024 * w for w in ws]
+                    if want is not None:
+                        assert valid[1::2] == [want] * len(ws), (seq, s)
+                    assert result[2] == len(ws)
+    finally:
+        c.close()
+
+
+@pytest.mark.parametrize("one_block", [False, True], ids=["default", "1-block-per-cu"])
+def test_bound_just_above_a_wave_edge(one_block):
+    """The batch's last message ends e = 1, 2, 3 bytes above an edge, so
+    d_count[1] = 1024 w + e and lane 63's `post` is read byte by byte: a
+    sequence that begins b bytes below the edge and ends whole with the
+    message (b + e its length), or is cut off by the message's end (b + e
+    less).  The same with msg_cap = d_count[1] exactly and BF, a continuation
+    byte, behind it in d_msg: read past the bound and taken for the message's,
+    it would turn a cut-off sequence into a valid one."""
+    c = _edge_codec(one_block)
+    try:
+        for w in _edge_waves(one_block):
+            for seq in (uc.EURO, uc.GRIN):
+                for b in range(1, len(seq)):
+                    for e in range(1, min(3, len(seq) - b) + 1):
+                        text = EDGE_BASE[:EDGE_AT] + seq[: b + e]
+                        want = len(text) if b + e == len(seq) else EDGE_AT
+                        batch = _edge_batch([(text, EDGE_AT, 1024 * w - b)])
+                        ref = model(batch)
+                        used = int(ref[1][1])
+                        assert used == 1024 * w + e
+                        _, valid, result = run(c, batch, ca.UTF8_TEXT, ref=ref)
+                        assert valid[1] == want and result[2:] == [1, len(text)], (w, seq, b, e)
+                        d_msg, d_msgs, d_count = decode(c, batch)
+                        torch.cuda.synchronize()
+                        assert (d_msg[used:] == SENTINEL).all().item()
+                        d_msg[used:] = 0xBF
+                        want_valid, want_result = expected(ref[0], ref[2], ca.UTF8_TEXT, used, batch.n)
+                        assert want_valid[1] == want
+                        check(c, d_msg, d_msgs, d_count, ca.UTF8_TEXT, used, batch.n, want_valid, want_result)
+                        assert c.sync_status() == 0
+    finally:
+        c.close()
