@@ -18,6 +18,8 @@ from .layout import (  # noqa: F401  (re-exported)
     STREAM_STATE, WS_BINARY, WS_CLOSE, WS_FIN, WS_PING, WS_PONG, WS_TEXT, WSG_EHIP, WSG_EINVAL, WSG_ENOMEM, WSG_ETRUNC,
     WSG_OK, UTF8_CLOSE, UTF8_EVERY, UTF8_TEXT, frame_plan, frame_size, frame_sizes, key_from_bytes, message_plan,
     reply_plan, utf8_plan,
+    PROTO_ANY, PROTO_CLIENT, PROTO_SERVER, PROTO_STATE, PROTO_VERDICT, PV_CLOSE_CODE, PV_CLOSE_LEN, PV_CLOSED, PV_CONT,
+    PV_CTRL_FRAGMENT, PV_CTRL_LONG, PV_DATA, PV_FRAME, PV_MASK, PV_NONE, PV_OPCODE, PV_RSV, PV_TOO_BIG, protocol_plan,
 )
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -71,6 +73,8 @@ def lib(path=None):
                                    ctypes.POINTER(u32), vp]),
         "wsg_check_utf8": (ci, [vp, vp, u64, vp, vp, u32, u32, vp, vp, vp]),
         "wsg_utf8_valid_up_to": (u64, [vp, u64]),
+        "wsg_check_protocol": (ci, [vp, vp, u64, vp, u32, vp, u32, vp, vp, u32, u64, vp, vp, vp]),
+        "wsg_proto_judge": (ci, [vp, vp, vp, u32, u64, vp, ctypes.POINTER(ctypes.c_uint16)]),
         "wsg_encode_batch": (ci, [vp, vp, vp, u32, vp, u64, vp, vp]),
         "wsg_fanout_encode": (ci, [vp, vp, u64, vp, u32, ctypes.c_uint8, ci, vp, u64, vp]),
         "wsg_fanout_encode_many": (ci, [vp, vp, vp, vp, vp, u32, vp, u32, ci, vp, u64, vp, vp]),
@@ -164,6 +168,31 @@ def utf8_valid_up_to(data):
     prefix of ``data`` (the host helper built from the rule the kernel runs)."""
     data = bytes(data)
     return int(lib().wsg_utf8_valid_up_to(data, len(data)))
+
+
+def proto_judge(info, wire, before, role=PROTO_ANY, max_message=0):
+    """wsg_proto_judge: one frame judged on the host by the rule the kernel
+    runs.  ``info``: one RECV_INFO record; ``wire``: the bytes its payload_off
+    indexes (a close frame's status is read from them; None: no wire);
+    ``before``: one PROTO_STATE record, or (bytes, open).  Returns (code,
+    status, after): the WSG_PV_* code (0: none), the close status that goes
+    with it and the PROTO_STATE behind the frame."""
+    rec = np.zeros(1, dtype=RECV_INFO)
+    rec[0] = info
+    st = np.zeros(2, dtype=PROTO_STATE)
+    if isinstance(before, tuple):
+        st["bytes"][0], st["open"][0] = before
+    else:
+        st[0] = before
+    if isinstance(wire, (bytes, bytearray)):
+        wire = np.frombuffer(bytes(wire), dtype=np.uint8)
+    buf = None if wire is None else np.ascontiguousarray(wire, dtype=np.uint8)
+    status = ctypes.c_uint16(0)
+    rc = lib().wsg_proto_judge(_np_ptr(rec), None if buf is None else _np_ptr(buf), _np_ptr(st[:1]), int(role),
+                               int(max_message), _np_ptr(st[1:]), ctypes.byref(status))
+    if rc < 0:
+        raise WSGError(rc, "wsg_proto_judge")
+    return rc, int(status.value), st[1].copy()
 
 
 class _Pinned:
@@ -331,6 +360,49 @@ class Codec:
                                     self._stream(stream))
         _check(rc, "wsg_check_utf8")
         return valid, result
+
+    # -- the frame-sequence rules of RFC 6455 ----------------------------------
+    def check_protocol(self, wire, info, n, stream_first, proto=None, role=PROTO_ANY, max_message=0, state=None,
+                       verdict=None, result=None, stream=None):
+        """wsg_check_protocol over what a decode left on the device: ``wire``
+        the batch's bytes, ``info`` the RECV_INFO bytes of its ``n`` frames,
+        ``stream_first`` int32[n_streams + 1] (no synchronisation needed after
+        the decode on the same stream).  ``proto``: uint8 CUDA tensor of
+        n_streams * 16 bytes (PROTO_STATE; None: zeros), each stream's state
+        before its first frame, updated in place to the state after its last
+        frame, or, with ``state`` (decode_messages' STREAM_STATE bytes), after
+        its last consumed frame.  ``role``: PROTO_*; ``max_message``: 0 for no
+        limit.  Returns (verdict, proto, result): the PROTO_VERDICT bytes (8
+        per stream, all 0xFF for a stream with no terminal frame), the new
+        states and int64[3] = [streams that violate, the lowest of them or
+        -1, streams closed cleanly]."""
+        t = self._torch
+        n = int(n)
+        ns = int(stream_first.numel()) - 1
+        if ns < 0 or stream_first.element_size() != 4:
+            raise WSGError(WSG_EINVAL, "check_protocol: stream_first must hold n_streams + 1 32-bit indices")
+        dev = info.device
+        if proto is None:
+            proto = t.zeros(max(ns, 1) * PROTO_STATE.itemsize, dtype=t.uint8, device=dev)
+        if verdict is None:
+            verdict = t.empty(max(ns, 1) * PROTO_VERDICT.itemsize, dtype=t.uint8, device=dev)
+        if result is None:
+            result = t.empty(3, dtype=t.int64, device=dev)
+        if (int(info.numel()) * info.element_size() < n * RECV_INFO.itemsize
+                or int(proto.numel()) * proto.element_size() < ns * PROTO_STATE.itemsize
+                or int(verdict.numel()) * verdict.element_size() < ns * PROTO_VERDICT.itemsize
+                or (state is not None and int(state.numel()) * state.element_size() < ns * STREAM_STATE.itemsize)
+                or int(result.numel()) < 3 or result.element_size() != 8):
+            raise WSGError(WSG_EINVAL, "check_protocol: a buffer is smaller than the batch needs")
+        rc = self._L.wsg_check_protocol(self._ctx, ctypes.c_void_p(wire.data_ptr()), wire.numel(),
+                                        ctypes.c_void_p(info.data_ptr()), n,
+                                        ctypes.c_void_p(stream_first.data_ptr()), ns,
+                                        ctypes.c_void_p(state.data_ptr()) if state is not None else None,
+                                        ctypes.c_void_p(proto.data_ptr()), int(role), int(max_message),
+                                        ctypes.c_void_p(verdict.data_ptr()), ctypes.c_void_p(result.data_ptr()),
+                                        self._stream(stream))
+        _check(rc, "wsg_check_protocol")
+        return verdict, proto, result
 
     # -- the device framer (raw stream bytes -> frame table -> messages) ------
     def _frame_args(self, what, wire, spans, frame_start, frame_cap, stream_first):

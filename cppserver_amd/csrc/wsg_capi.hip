@@ -90,6 +90,10 @@ struct wsg_ctx {
     uint64_t* d_frame_plan = nullptr;
     uint64_t frame_plan_cap = 0;
     wsg_scratch_order frame_order;   // wsg_frame_streams calls
+    // wsg_check_protocol: the frames' streams, scan partials, per-stream states (wsg::proto_plan_layout)
+    uint8_t* d_proto_plan = nullptr;
+    uint64_t proto_plan_cap = 0;
+    wsg_scratch_order proto_order;   // wsg_check_protocol calls
     // staging for host entry points
     uint8_t* d_stage = nullptr;
     uint8_t* h_stage = nullptr;
@@ -1092,9 +1096,10 @@ int wsg_destroy(wsg_ctx* c)
     if (c->h_err_copy)
         (void)hipHostFree(c->h_err_copy);
     free_enc(c->enc);
-    for (hipEvent_t ev : {c->enc_order.done, c->msg_order.done, c->frame_order.done})
+    for (hipEvent_t ev : {c->enc_order.done, c->msg_order.done, c->frame_order.done, c->proto_order.done})
         if (ev)
             (void)hipEventDestroy(ev);
+    (void)hipFree(c->d_proto_plan);
     (void)hipFree(c->d_frame_plan);
     (void)hipFree(c->d_msg_plan);
     (void)hipFree(c->d_msg_pieces);
@@ -1285,6 +1290,48 @@ int wsg_check_utf8(wsg_ctx* c, const uint8_t* d_msg, uint64_t msg_cap, const wsg
     }
     WSG_HIP(wsg::launch_utf8_count(s, rec_grid, d_msgs, d_count, msg_room, msg_cap, which, d_valid, d_result));
     return WSG_OK;
+}
+
+// The frame-sequence rules over a decoded batch: a scan of the frames' steps
+// on their stream's state, the judging kernel (one lane per frame), one lane
+// per stream behind it.
+int wsg_check_protocol(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const wsg_recv_info* d_info, uint32_t n,
+                       const uint32_t* d_stream_first, uint32_t n_streams, const wsg_stream_state* d_state,
+                       wsg_proto_state* d_proto, uint32_t role, uint64_t max_message, wsg_proto_verdict* d_verdict,
+                       uint64_t* d_result, void* stream)
+{
+    if (!c || !d_info || !d_stream_first || !d_proto || !d_verdict || !d_result || (wire_len && !d_wire) ||
+        role > WSG_PROTO_CLIENT || n == UINT32_MAX || n_streams == UINT32_MAX)
+        return WSG_EINVAL;
+    if (!aligned8(d_info) || (reinterpret_cast<uintptr_t>(d_stream_first) & 3u) || !aligned8(d_state) ||
+        !aligned8(d_proto) || !aligned8(d_verdict) || !aligned8(d_result))
+        return WSG_EINVAL;
+    if (c->check && (!in_alloc(d_wire, wire_len) || !in_alloc(d_info, uint64_t(n) * sizeof(wsg_recv_info)) ||
+                     !in_alloc(d_stream_first, (uint64_t(n_streams) + 1) * 4) ||
+                     (d_state && !in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state))) ||
+                     !in_alloc(d_proto, uint64_t(n_streams) * sizeof(wsg_proto_state)) ||
+                     !in_alloc(d_verdict, uint64_t(n_streams) * sizeof(wsg_proto_verdict)) || !in_alloc(d_result, 3 * 8)))
+        return WSG_EINVAL;
+    hipStream_t s = pick(c, stream);
+    if (int rc = ensure_array(c->d_proto_plan, c->proto_plan_cap, wsg::proto_plan_layout(nullptr, n, n_streams, nullptr)))
+        return rc;
+    wsg::ProtoPlan plan;
+    wsg::proto_plan_layout(c->d_proto_plan, n, n_streams, &plan);
+    // the plan is the context's: behind the previous call's kernels, whatever
+    // stream they ran on
+    bool ordered = false;
+    if (int rc = scratch_enter(c->proto_order, s, &ordered))
+        return rc;
+    WSG_HIP(wsg::launch_proto_scan(s, d_info, n, d_stream_first, n_streams, d_proto, plan, d_verdict, d_result));
+    if (n && n_streams) {
+        const int t = timing_begin(c, s);
+        WSG_HIP(wsg::launch_proto_judge(s, d_wire, wire_len, d_info, n, d_stream_first, d_state, d_proto, role,
+                                        max_message, plan, d_verdict));
+        timing_end(c, s, t);
+    }
+    WSG_HIP(wsg::launch_proto_finish(s, grid_for(c, ceil_div(n_streams, wsg::BLOCK)), n, d_stream_first, n_streams,
+                                     d_state, d_proto, plan, d_verdict, d_result));
+    return scratch_leave(c->proto_order, s, ordered);
 }
 
 // The device framer: two walks over every stream (one wave each) with a scan

@@ -1,7 +1,7 @@
 // wsg_device.h — device helpers shared by the kernel sources (wsg_kernels.hip,
-// wsg_messages.hip, wsg_frames.hip, wsg_utf8.hip): 16-byte loads and stores,
-// byte funnels, the frame parse, the block scan, the error latch and the
-// wsg_msg record codec.  Internal linkage: every source gets its own copy.
+// wsg_messages.hip, wsg_frames.hip, wsg_utf8.hip, wsg_proto.hip): 16-byte loads
+// and stores, byte funnels, the frame parse, the block scan, the wave
+// reductions, the stream search, the error latch and the wsg_msg record codec.  Internal linkage: every source gets its own copy.
 #pragma once
 
 #include <type_traits>
@@ -318,6 +318,40 @@ __device__ __forceinline__ T scan_partials(const T* __restrict__ in, T* __restri
         carry = op(carry, tot);
     }
     return carry;
+}
+
+// Sum and minimum over the wave, in lane 0.
+__device__ __forceinline__ uint64_t wave_sum(uint64_t v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1)
+        v += __shfl_down(v, d, 64);
+    return v;   // lane 0
+}
+
+__device__ __forceinline__ uint64_t wave_min(uint64_t v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint64_t u = __shfl_down(v, d, 64);
+        v = u < v ? u : v;
+    }
+    return v;   // lane 0
+}
+
+// Last j < ns with sf[j] <= i (0 when there is none): the stream of frame i
+// (an empty stream shares its first index with the next one, which wins).
+__device__ __forceinline__ uint32_t stream_of(const uint32_t* __restrict__ sf, uint32_t ns, uint32_t i)
+{
+    uint32_t lo = 0, hi = ns;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (sf[mid] <= i)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
 }
 
 // The error latch wsg_sync decodes: the smallest (index << 8 | -code) wins,

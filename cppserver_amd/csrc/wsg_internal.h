@@ -1,6 +1,6 @@
 // wsg_internal.h — kernel geometry and kernel declarations shared by the
 // kernel sources (wsg_kernels.hip, wsg_messages.hip, wsg_frames.hip,
-// wsg_utf8.hip) and the C-ABI implementation.
+// wsg_utf8.hip, wsg_proto.hip) and the C-ABI implementation.
 #pragma once
 
 #include "wsg_frame.h"
@@ -183,6 +183,36 @@ hipError_t launch_utf8_scan(hipStream_t s, int grid, const uint8_t* msg, uint64_
 // records checked and their bytes.
 hipError_t launch_utf8_count(hipStream_t s, int grid, const wsg_msg* msgs, const uint64_t* count, uint32_t msg_room,
                              uint64_t msg_cap, uint32_t which, const uint64_t* valid, uint64_t* result);
+
+// ---- protocol rules on the device (wsg_check_protocol; wsg_proto.hip) -------
+struct ProtoStep;   // wsg_proto.h
+// Scratch of one call, carved by the host out of one device block
+// (proto_plan_layout; one block = BLOCK frames).
+struct ProtoPlan {
+    ProtoStep* part;   // nb: the blocks' composed steps
+    ProtoStep* pre;    // nb: their exclusive prefixes
+    uint64_t* out;     // 2 * ns: the state d_proto[j] gets, as its two words (k_proto_judge to k_proto_finish)
+    uint32_t* sidx;    // n: the frame's stream
+};
+// Bytes of that block for n frames in ns streams; plan (or null) gets the pointers into base.
+uint64_t proto_plan_layout(uint8_t* base, uint32_t n, uint32_t ns, ProtoPlan* plan);
+// k_proto_local and k_proto_blocks: d_verdict and d_result seeded (all 0xFF;
+// {0, UINT64_MAX, 0}), the frames' streams and the scanned block partials in
+// the plan.  At least one block, also for n == 0 or n_streams == 0.
+hipError_t launch_proto_scan(hipStream_t s, const wsg_recv_info* info, uint32_t n, const uint32_t* stream_first,
+                             uint32_t n_streams, const wsg_proto_state* proto, const ProtoPlan& plan,
+                             wsg_proto_verdict* verdict, uint64_t* result);
+// The per-frame judging kernel (n > 0 and n_streams > 0): every frame's code,
+// the first of each stream into d_verdict by atomicMin; the state d_proto asks
+// for into the plan.
+hipError_t launch_proto_judge(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const wsg_recv_info* info,
+                              uint32_t n, const uint32_t* stream_first, const wsg_stream_state* state,
+                              const wsg_proto_state* proto, uint32_t role, uint64_t max_message, const ProtoPlan& plan,
+                              wsg_proto_verdict* verdict);
+// One lane per stream (grid-stride): d_proto and d_result's counts.
+hipError_t launch_proto_finish(hipStream_t s, int grid, uint32_t n, const uint32_t* stream_first, uint32_t n_streams,
+                               const wsg_stream_state* state, wsg_proto_state* proto, const ProtoPlan& plan,
+                               const wsg_proto_verdict* verdict, uint64_t* result);
 
 // ---- fan-out, XOR, offset rebase, test hook (wsg_kernels.hip) ---------------
 // Messages of one fan-out launch (blockIdx.y): payload and output offsets.

@@ -57,21 +57,6 @@ namespace wsg {
 
 namespace {
 
-// Last j < ns with sf[j] <= i (0 when there is none): the stream of frame i
-// (an empty stream shares its first index with the next one, which wins).
-__device__ __forceinline__ uint32_t stream_of(const uint32_t* __restrict__ sf, uint32_t ns, uint32_t i)
-{
-    uint32_t lo = 0, hi = ns;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (sf[mid] <= i)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
 // Batch-wide values of the plan's block-local scans, for k in [0, n].
 __device__ __forceinline__ uint64_t fins_before(const MsgPlan& P, uint32_t n, uint32_t k)
 {

@@ -132,24 +132,6 @@ __device__ __forceinline__ uint32_t utf8_chunk_bad(uint32_t pre, v4u c, uint32_t
     return bad;
 }
 
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-        v += __shfl_down(v, d, 64);
-    return v;   // lane 0
-}
-
-__device__ __forceinline__ uint64_t wave_min(uint64_t v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint64_t u = __shfl_down(v, d, 64);
-        v = u < v ? u : v;
-    }
-    return v;   // lane 0
-}
-
 } // namespace
 
 // One lane per record (grid-stride): d_valid[m] = len; the first lane seeds

@@ -1,7 +1,8 @@
 """Record layouts shared by the C-ABI (include/wsg_capi.h) and its callers.
 
 numpy structured dtypes whose byte layout is exactly ``wsg_send_desc``,
-``wsg_recv_info``, ``wsg_msg``, ``wsg_stream_state`` and ``wsg_stream_span``;
+``wsg_recv_info``, ``wsg_msg``, ``wsg_stream_state``, ``wsg_stream_span``,
+``wsg_proto_state`` and ``wsg_proto_verdict``;
 importing this module loads no native code.
 """
 import numpy as np
@@ -329,3 +330,125 @@ def utf8_plan(msgs, msg_bytes, which, msg_cap=None):
             invalid += 1
             lowest = min(lowest, m)
     return valid, np.array([invalid, lowest, checked, nbytes], dtype=np.uint64)
+
+
+# wsg_check_protocol (include/wsg_capi.h): the per-stream state, the verdict
+# and the WSG_PV_* / WSG_PROTO_* constants.
+PROTO_STATE = np.dtype([("bytes", "<u8"), ("open", "u1"), ("_pad", "u1", (7,))])
+PROTO_VERDICT = np.dtype([("code", "u1"), ("_pad", "u1"), ("status", "<u2"), ("frame", "<u4")])
+
+assert PROTO_STATE.itemsize == 16 and PROTO_VERDICT.itemsize == 8
+
+(PV_CLOSED, PV_FRAME, PV_RSV, PV_OPCODE, PV_MASK, PV_CTRL_FRAGMENT, PV_CTRL_LONG, PV_CONT, PV_DATA, PV_CLOSE_LEN,
+ PV_CLOSE_CODE, PV_TOO_BIG) = range(1, 13)
+PV_NONE = 0xFF
+PROTO_ANY, PROTO_SERVER, PROTO_CLIENT = 0, 1, 2
+
+
+def protocol_plan(info, stream_first, proto_in, role, max_message, wire, consumed=None):
+    """wsg_check_protocol restated on the host in vectorised numpy: no loop
+    over frames or streams; a frame's state comes from running maxima (the
+    last frame that set the byte count, the last that set `open`) and a
+    running sum, as the kernels' comes from a scan.
+
+    ``info``: RECV_INFO of the batch's frames; ``stream_first``: n_streams + 1
+    frame indices; ``proto_in``: PROTO_STATE per stream (None: zeros);
+    ``wire``: the bytes payload_off indexes (read for close statuses only);
+    ``consumed``: per stream, as STREAM_STATE.consumed (None: the state after
+    each stream's last frame).  Returns (verdict, proto_out, result):
+    PROTO_VERDICT and PROTO_STATE per stream and result = [streams whose
+    terminal frame is a violation, the lowest of them or 2**64 - 1, streams
+    closed cleanly]."""
+    info = np.asarray(info, dtype=RECV_INFO)
+    n = len(info)
+    sf = np.minimum(np.asarray(stream_first, dtype=np.int64), n)
+    ns = len(sf) - 1
+    seed = np.zeros(ns, dtype=PROTO_STATE)
+    if proto_in is not None:
+        seed["bytes"] = np.asarray(proto_in, dtype=PROTO_STATE)["bytes"]
+        seed["open"] = np.asarray(proto_in, dtype=PROTO_STATE)["open"] != 0
+    verdict = np.frombuffer(b"\xff" * (8 * ns), dtype=PROTO_VERDICT).copy()
+    proto_out = seed.copy()
+    result = np.array([0, U64_MAX, 0], dtype=np.uint64)
+    if ns == 0 or n == 0:
+        return verdict, proto_out, result
+    idx = np.arange(n, dtype=np.int64)
+    sidx = np.maximum(np.searchsorted(sf[:ns], idx, side="right") - 1, 0)   # the last j with sf[j] <= i
+    head = sf[sidx]
+    op = info["opcode"].astype(np.int64)
+    fin = info["fin"] != 0
+    masked = info["masked"] != 0
+    error = info["error"] != 0
+    rsv = (info["b0"] & 0x70) != 0
+    length = info["len"].astype(object)                                       # Python integers: sums do not wrap
+    keep = error | (op > 2)
+    sets = ~keep & (op != 0)
+    adds = ~keep & (op == 0)
+
+    def last_before(flag):
+        """Per frame: the last flagged frame in front of it in its stream, -1 when there is none."""
+        inc = np.maximum.accumulate(np.where(flag, idx, -1))
+        ex = np.concatenate([[-1], inc[:-1]])
+        return np.where(ex >= head, ex, -1)
+
+    p_set, p_any = last_before(sets), last_before(~keep)
+    add_sum = np.concatenate([[0], np.cumsum(np.where(adds, length, 0).astype(object))])   # of the frames before k
+    base = np.where(p_set >= 0, length[np.maximum(p_set, 0)], seed["bytes"][sidx].astype(object))
+    since = np.where(p_set >= 0, p_set + 1, head)
+    before = np.minimum(base + (add_sum[idx] - add_sum[since]), U64_MAX)
+    open_before = np.where(p_any >= 0, ~fin[np.maximum(p_any, 0)], seed["open"][sidx] != 0)
+    after = np.where(keep, before, np.where(sets, length, np.minimum(before + length, U64_MAX)))
+    open_after = np.where(keep, open_before, ~fin)
+
+    # the close status on the wire
+    wire = np.asarray(wire, dtype=np.uint8)
+    po = info["payload_off"]
+    has_status = (op == WS_CLOSE) & (info["len"] >= 2) & (len(wire) >= 2) & (po <= np.uint64(max(len(wire) - 2, 0)))
+    carried = np.zeros(n, dtype=np.int64)                                     # (two bytes past the wire: read as 0)
+    at = po[has_status].astype(np.int64)
+    key = info["key"][has_status].astype(np.int64) * masked[has_status]
+    carried[has_status] = ((wire[at].astype(np.int64) ^ (key & 0xFF)) << 8) | (wire[at + 1] ^ ((key >> 8) & 0xFF))
+    status_ok = ((carried >= 1000) & (carried <= 1003)) | ((carried >= 1007) & (carried <= 1014)) | \
+        ((carried >= 3000) & (carried <= 4999))
+
+    control = (op & 8) != 0
+    reserved = ((op >= 3) & (op <= 7)) | (op >= 0xB)
+    data = op <= 2
+    rules = [
+        (error, PV_FRAME),
+        (rsv, PV_RSV),
+        (reserved, PV_OPCODE),
+        (~masked if role == PROTO_SERVER else masked if role == PROTO_CLIENT else np.zeros(n, dtype=bool), PV_MASK),
+        (control & ~fin, PV_CTRL_FRAGMENT),
+        (control & (length > 125), PV_CTRL_LONG),
+        ((op == 0) & ~open_before, PV_CONT),
+        (data & (op != 0) & open_before, PV_DATA),
+        ((op == WS_CLOSE) & (length == 1), PV_CLOSE_LEN),
+        ((op == WS_CLOSE) & (length >= 2) & ~status_ok, PV_CLOSE_CODE),
+        (data & (after > max_message) if max_message else np.zeros(n, dtype=bool), PV_TOO_BIG),
+        (op == WS_CLOSE, PV_CLOSED),
+    ]
+    code = np.select([r[0].astype(bool) for r in rules], [r[1] for r in rules], 0)
+    status = np.where(code == PV_TOO_BIG, 1009, np.where(code == PV_CLOSED, np.where(length == 0, 1005, carried), 1002))
+
+    judged = np.nonzero(code)[0]                                              # ascending: a stream's first comes first
+    streams, first = np.unique(sidx[judged], return_index=True)
+    term = judged[first]
+    verdict["code"][streams] = code[term]
+    verdict["_pad"][streams] = 0
+    verdict["status"][streams] = status[term].astype(np.int64)
+    verdict["frame"][streams] = term
+
+    start, end = sf[:-1], np.maximum(sf[1:], sf[:-1])
+    target = end if consumed is None else start + np.asarray(consumed, dtype=np.int64)
+    has = (target > start) & (target <= end)
+    last = np.maximum(target - 1, 0)[has]
+    proto_out["bytes"][has] = after[last].astype(np.uint64)
+    proto_out["open"][has] = open_after[last].astype(bool)
+
+    bad = verdict["code"][streams] >= PV_FRAME
+    result[0] = int(bad.sum())
+    if bad.any():
+        result[1] = int(streams[bad].min())
+    result[2] = int((verdict["code"][streams] == PV_CLOSED).sum())
+    return verdict, proto_out, result

@@ -23,7 +23,8 @@
  * frame map), wsg_decode_messages and wsg_reply_messages calls another (plan
  * block, piece records) and wsg_frame_streams calls a third (per-stream frame
  * counts, scan partials; wsg_decode_streams and wsg_reply_streams are one
- * call of each of the last two);
+ * call of each of the last two) and wsg_check_protocol calls a fourth (the
+ * frames' streams, scan partials, per-stream states);
  * wsg_decode_batch, wsg_check_utf8 and the fan-out calls use none.  The calls that
  * share a scratch are ordered across streams on the device, in the order they
  * were made: a call on another stream than the previous one first waits
@@ -33,7 +34,7 @@
  * is capturing is not ordered: it neither waits nor records, so the caller
  * keeps other users of that scratch off the device while the graph runs.  A
  * graph holding wsg_encode_batch / wsg_decode_messages / wsg_reply_messages /
- * wsg_frame_streams launches (wsg_decode_streams and wsg_reply_streams
+ * wsg_frame_streams / wsg_check_protocol launches (wsg_decode_streams and wsg_reply_streams
  * synchronise and cannot be captured) names the
  * scratch addresses it was captured with; a later call that needs a larger
  * scratch frees them (after a device synchronise), and the graph must not be
@@ -387,6 +388,111 @@ int wsg_check_utf8(wsg_ctx* ctx, const uint8_t* d_msg, uint64_t msg_cap,
 /* Length of the longest well-formed UTF-8 prefix of buf[0..len) (RFC 3629);
  * len when the whole buffer is valid.  Host; the rule the kernel runs. */
 uint64_t wsg_utf8_valid_up_to(const uint8_t* buf, uint64_t len);
+
+/* ---- protocol: the frame-sequence rules of RFC 6455 checked on the device -- */
+/* (Added without an ABI bump, as wsg_decode_messages was: symbols, structs and
+ * constants only.)
+ *
+ * RFC 6455 5.1, 5.2, 5.4, 5.5 and 7.4 (Autobahn groups 2-5 and 7): an endpoint
+ * fails a connection with status 1002 for RSV bits without an extension, a
+ * reserved opcode, a client frame that is not masked (a server frame that is),
+ * a fragmented or over-long control frame, a continuation with nothing to
+ * continue, a new data frame inside a message, a close frame with a 1-byte
+ * body or an illegal status; with 1009 when a message outgrows its limit.  The
+ * reference accepts all of these, so this is a call of its own behind a decode
+ * (wsg_decode_batch, wsg_decode_messages, wsg_reply_messages or the _streams
+ * forms), from the d_info and d_stream_first it left on the device and two
+ * wire bytes per close frame; no synchronisation is needed in between on one
+ * stream.
+ *
+ * State.  Before a frame a stream is (open, bytes): a data message (opcode 1
+ * or 2) has begun and not had its FIN frame, and that message's payload bytes
+ * so far.  With op = opcode, rsv = b0 & 0x70, a frame leaves the state
+ * unchanged when error != 0, op & 8 (control) or op is reserved (3-7, 0xB-0xF);
+ * op 1 or 2: bytes = len, open = !fin; op 0: bytes += len (saturating at
+ * UINT64_MAX), open = !fin.  The transition applies whether or not the frame
+ * violates a rule.
+ * Judgement.  A frame's code is the lowest-numbered WSG_PV_* below that
+ * applies (a violation wins over WSG_PV_CLOSED); the status is 1002 for codes
+ * 2-11, 1009 for WSG_PV_TOO_BIG and for WSG_PV_CLOSED the status the close
+ * frame carries (1005 when it is empty): d_wire[payload_off] and
+ * d_wire[payload_off + 1], each XOR the key's bytes 0 and 1 when masked, taken
+ * big-endian; the legal ones are 1000-1003, 1007-1014 and 3000-4999.  A
+ * stream's terminal frame is its first frame with any code; frames behind it
+ * are not judged.
+ * Outputs.  d_verdict[j]: stream j's terminal frame (`frame` its index in the
+ * frame table), all eight bytes 0xFF when it has none (frame == UINT32_MAX,
+ * code == WSG_PV_NONE).  d_proto[j] is read as the state before the stream's
+ * first frame (open: non-zero) and written as the state after its last frame,
+ * or, with d_state (as wsg_decode_messages left it), after frame
+ * d_stream_first[j] + d_state[j].consumed - 1, the incoming state when
+ * consumed == 0: the state at the point from which the caller resubmits the
+ * tail.  Every frame of the stream is judged all the same, and judging the
+ * tail again in the next call gives the same verdicts.  d_result[0..3): the
+ * streams whose terminal frame is a violation (code >= 2), the lowest such
+ * stream (UINT64_MAX when there is none), the streams that closed cleanly.
+ * Minima and counts: deterministic.
+ * role: WSG_PROTO_ANY (no mask rule), WSG_PROTO_SERVER (judging frames a client
+ * sent) or WSG_PROTO_CLIENT.  max_message: 0 for no limit.
+ * Asynchronous on `stream`.  Latches nothing: a violation is a result, and
+ * wsg_sync is unaffected.  n == 0, n_streams == 0 and empty streams are valid
+ * (an empty stream keeps its state and gets the all-0xFF verdict; with
+ * n_streams == 0 no frame is judged).  A close status whose two bytes do not
+ * lie below wire_len is read as 0.  WSG_EINVAL for a NULL operand other than
+ * d_state (d_wire may be NULL when wire_len == 0), a misaligned one (8 bytes;
+ * d_stream_first 4) or a role above 2.
+ * Streams: the calls share a scratch of the ctx (the frames' streams, scan
+ * partials, per-stream states) and are ordered across streams on the device
+ * like the wsg_encode_batch and wsg_decode_messages calls (see "Streams"
+ * above), with the same capture rule: a captured call is not ordered, and a
+ * call that has to grow the scratch must not be captured: run it once with
+ * the same n and n_streams first.                                           */
+#define WSG_PV_CLOSED         1   /* a legal close frame: not a violation     */
+#define WSG_PV_FRAME          2   /* d_info[i].error != 0                     */
+#define WSG_PV_RSV            3
+#define WSG_PV_OPCODE         4
+#define WSG_PV_MASK           5
+#define WSG_PV_CTRL_FRAGMENT  6
+#define WSG_PV_CTRL_LONG      7
+#define WSG_PV_CONT           8
+#define WSG_PV_DATA           9
+#define WSG_PV_CLOSE_LEN      10
+#define WSG_PV_CLOSE_CODE     11
+#define WSG_PV_TOO_BIG        12
+#define WSG_PV_NONE           0xFF  /* d_verdict: the stream has no terminal frame */
+
+#define WSG_PROTO_ANY     0u
+#define WSG_PROTO_SERVER  1u  /* the frames came from a client: they must be masked */
+#define WSG_PROTO_CLIENT  2u  /* the frames came from a server: they must not be    */
+
+typedef struct wsg_proto_state {   /* 16 bytes */
+    uint64_t bytes;        /* payload bytes of the open message so far               */
+    uint8_t  open;         /* a data message has begun and not had its FIN frame     */
+    uint8_t  _pad[7];      /* written as 0 */
+} wsg_proto_state;
+
+typedef struct wsg_proto_verdict { /* 8 bytes; as one little-endian uint64 it orders by frame first */
+    uint8_t  code;         /* WSG_PV_*                                               */
+    uint8_t  _pad;
+    uint16_t status;       /* the close status the endpoint answers with             */
+    uint32_t frame;        /* index of the terminal frame in the frame table         */
+} wsg_proto_verdict;
+
+int wsg_check_protocol(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
+                       const wsg_recv_info* d_info, uint32_t n,
+                       const uint32_t* d_stream_first, uint32_t n_streams,
+                       const wsg_stream_state* d_state /* or NULL */,
+                       wsg_proto_state* d_proto, uint32_t role, uint64_t max_message,
+                       wsg_proto_verdict* d_verdict, uint64_t* d_result, void* stream);
+
+/* One frame judged on the host by the rule the kernel runs: info its record,
+ * wire the buffer info->payload_off indexes (read only for a close frame's
+ * status; may be NULL otherwise), before the stream's state in front of it.
+ * Returns the frame's code (0: none) or WSG_EINVAL; *after (or NULL) gets the
+ * state behind the frame, *status (or NULL) the status that goes with the
+ * code (0 with code 0).                                                     */
+int wsg_proto_judge(const wsg_recv_info* info, const uint8_t* wire, const wsg_proto_state* before,
+                    uint32_t role, uint64_t max_message, wsg_proto_state* after, uint16_t* status);
 
 /* ---- batch encode: header pack + mask (PrepareSendFrame over many frames) */
 /* Frames are written back to back into d_wire (16-byte aligned, capacity

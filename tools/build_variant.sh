@@ -13,7 +13,7 @@ F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -I$root/include $*"
 csrc=$root/cppserver_amd/csrc
 $H $F -I$csrc -c ${KSRC:-$csrc/wsg_kernels.hip} -o k.o
 pobjs=
-for p in ${PSRC-$csrc/wsg_messages.hip $csrc/wsg_frames.hip $csrc/wsg_utf8.hip}; do
+for p in ${PSRC-$csrc/wsg_messages.hip $csrc/wsg_frames.hip $csrc/wsg_utf8.hip $csrc/wsg_proto.hip}; do
     o=p_$(basename "$p" .hip).o
     $H $F -I$csrc -c "$p" -o "$o"
     pobjs="$pobjs $o"
@@ -26,5 +26,6 @@ $H -O3 -std=c++17 -fPIC -I$root/include -c $root/cppserver_amd/csrc/http.cpp -o 
 $H -O3 -std=c++17 -fPIC -I$root/include -c $root/cppserver_amd/csrc/tls.cpp -o t.o
 $H -O3 -std=c++17 -fPIC -I$root/include -c $root/cppserver_amd/csrc/wss.cpp -o s.o
 $H -O3 -std=c++17 -fPIC -I$root/include -c $root/cppserver_amd/csrc/wsg_mgpu.cpp -o m.o
-$H --offload-arch=gfx950 -shared -o libwsg.so k.o $pobjs c.o w.o a.o b.o h.o t.o s.o m.o -lssl -lcrypto -ldl -L/opt/rocm/lib -lrocprofiler-sdk-roctx
+$H -O3 -std=c++17 -fPIC -I$root/include -c $root/cppserver_amd/csrc/wsg_proto_host.cpp -o j.o
+$H --offload-arch=gfx950 -shared -o libwsg.so k.o $pobjs c.o w.o a.o b.o h.o t.o s.o m.o j.o -lssl -lcrypto -ldl -L/opt/rocm/lib -lrocprofiler-sdk-roctx
 echo "$out/libwsg.so"

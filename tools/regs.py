@@ -1,6 +1,7 @@
 """Register/occupancy report for k_decode and source variants with paths cut
 out (which path sets the kernel's VGPR count), and for k_msg_gather
-(wsg_decode_messages; wsg_reply_messages runs it too) and the reply plan.  Compiles for gfx950 only (no GPU needed).
+(wsg_decode_messages; wsg_reply_messages runs it too), the reply plan, the
+framer, the UTF-8 check and the protocol check.  Compiles for gfx950 only (no GPU needed).
 
 usage: python tools/regs.py
 """
@@ -34,8 +35,9 @@ def report(text, tag, kernel="_ZN3wsg8k_decode"):
     def g(k):
         m = re.search(k + r": (\d+)", block)
         return m.group(1) if m else "?"
-    print("%-28s VGPR %s SGPR %s sspill %s vspill %s occ %s" % (
-        tag, g(" VGPRs"), g("TotalSGPRs"), g("SGPRs Spill"), g("VGPRs Spill"), g(r"Occupancy \[waves/SIMD\]")))
+    print("%-28s VGPR %s SGPR %s sspill %s vspill %s scratch %s occ %s" % (
+        tag, g(" VGPRs"), g("TotalSGPRs"), g("SGPRs Spill"), g("VGPRs Spill"), g(r"ScratchSize \[bytes/lane\]"),
+        g(r"Occupancy \[waves/SIMD\]")))
 
 
 def cut(text, marker):
@@ -54,7 +56,8 @@ if __name__ == "__main__":
     for name, kernels in (("wsg_messages.hip", ("k_msg_gather", "k_msg_finalize", "k_reply_local", "k_reply_blocks",
                                                 "k_reply_finalize")),
                           ("wsg_frames.hip", ("k_frame_count", "k_frame_write")),
-                          ("wsg_utf8.hip", ("k_utf8_init", "k_utf8_scan", "k_utf8_count"))):
+                          ("wsg_utf8.hip", ("k_utf8_init", "k_utf8_scan", "k_utf8_count")),
+                          ("wsg_proto.hip", ("k_proto_local", "k_proto_blocks", "k_proto_judge", "k_proto_finish"))):
         src = source(name)
         for k in kernels:
             report(src, k, kernel="_ZN3wsg%d%s" % (len(k), k))
