@@ -20,6 +20,7 @@ from .layout import (  # noqa: F401  (re-exported)
     reply_plan, utf8_plan,
     PROTO_ANY, PROTO_CLIENT, PROTO_SERVER, PROTO_STATE, PROTO_VERDICT, PV_CLOSE_CODE, PV_CLOSE_LEN, PV_CLOSED, PV_CONT,
     PV_CTRL_FRAGMENT, PV_CTRL_LONG, PV_DATA, PV_FRAME, PV_MASK, PV_NONE, PV_OPCODE, PV_RSV, PV_TOO_BIG, protocol_plan,
+    PV_UTF8, checked_reply_plan, merge_verdicts, utf8_verdicts,
 )
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -71,6 +72,11 @@ def lib(path=None):
         "wsg_reply_messages": (ci, [vp, vp, u64, vp, u32, vp, u32, vp, vp, ci, vp, vp, u64, vp, vp, vp, vp, vp, vp]),
         "wsg_reply_streams": (ci, [vp, vp, u64, vp, u32, vp, vp, u32, vp, vp, ci, vp, vp, u64, vp, vp, vp, vp, vp,
                                    ctypes.POINTER(u32), vp]),
+        "wsg_reply_checked": (ci, [vp, vp, u64, vp, u32, vp, u32, vp, vp, u32, u64, vp, vp, ci, vp, vp, u64, vp, vp, vp,
+                                   vp, vp, vp, vp, vp, vp]),
+        "wsg_reply_checked_streams": (ci, [vp, vp, u64, vp, u32, vp, vp, u32, vp, vp, u32, u64, vp, ci, vp, vp, u64, vp,
+                                           vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(u32), vp]),
+        "wsg_utf8_verdicts": (ci, [vp, vp, vp, u32, u32, vp, u32, vp, vp]),
         "wsg_check_utf8": (ci, [vp, vp, u64, vp, vp, u32, u32, vp, vp, vp]),
         "wsg_utf8_valid_up_to": (u64, [vp, u64]),
         "wsg_check_protocol": (ci, [vp, vp, u64, vp, u32, vp, u32, vp, vp, u32, u64, vp, vp, vp]),
@@ -576,6 +582,115 @@ class Codec:
                                        self._stream(stream))
         _check(rc, "wsg_reply_streams")
         return reply, reply_off, stream_reply, msgs, count, state, info, frame_start, stream_first, n.value
+
+    # -- checked replies (reply_messages with check_protocol inside it) --------
+    def _checked_args(self, what, dev, ns, proto, close_off, verdict, result, count):
+        t = self._torch
+        if proto is None:
+            proto = t.zeros(max(ns, 1) * PROTO_STATE.itemsize, dtype=t.uint8, device=dev)
+        if close_off is None:
+            close_off = t.empty(max(ns, 1), dtype=t.int64, device=dev)
+        if verdict is None:
+            verdict = t.empty(max(ns, 1) * PROTO_VERDICT.itemsize, dtype=t.uint8, device=dev)
+        if result is None:
+            result = t.empty(3, dtype=t.int64, device=dev)
+        if count is None:
+            count = t.empty(5, dtype=t.int64, device=dev)
+        if (int(proto.numel()) * proto.element_size() < ns * PROTO_STATE.itemsize
+                or int(close_off.numel()) < ns or close_off.element_size() != 8
+                or int(verdict.numel()) * verdict.element_size() < ns * PROTO_VERDICT.itemsize
+                or int(result.numel()) < 3 or result.element_size() != 8
+                or int(count.numel()) < 5 or count.element_size() != 8):
+            raise WSGError(WSG_EINVAL, "%s: a buffer is smaller than the batch needs" % what)
+        return proto, close_off, verdict, result, count
+
+    def reply_checked(self, wire, frame_start, stream_first, proto=None, role=PROTO_ANY, max_message=0, also=None,
+                      reply_op=ECHO_REPLY, mask=False, send_keys=None, state=None, reply=None, reply_cap=None,
+                      stream=None, reply_off=None, stream_reply=None, close_off=None, verdict=None, result=None,
+                      msgs=None, count=None, info=None):
+        """wsg_reply_checked: reply_messages with check_protocol run inside
+        it.  Replies stop at a stream's terminal frame, where the stream gets
+        a close frame with the verdict's status.  ``proto`` / ``role`` /
+        ``max_message`` as check_protocol; ``also``: PROTO_VERDICT bytes per
+        stream (utf8_verdicts' output) or None; the rest as reply_messages.
+        Returns (reply, reply_off, stream_reply, close_off, verdict, proto,
+        result, msgs, count, state, info): close_off int64[n_streams] (-1: no
+        close frame), count int64[5] = [messages, dense bytes, reply bytes,
+        reply frames, close frames]."""
+        n = int(frame_start.numel())
+        ns = int(stream_first.numel()) - 1
+        if ns < 0 or stream_first.element_size() != 4:
+            raise WSGError(WSG_EINVAL, "reply_checked: stream_first must hold n_streams + 1 32-bit indices")
+        proto, close_off, verdict, result, count = self._checked_args("reply_checked", wire.device, ns, proto,
+                                                                      close_off, verdict, result, count)
+        if also is not None and int(also.numel()) * also.element_size() < ns * PROTO_VERDICT.itemsize:
+            raise WSGError(WSG_EINVAL, "reply_checked: also must hold n_streams verdicts")
+        rule, cap, reply, reply_off, stream_reply, state, msgs, count, info = self._reply_args(
+            "reply_checked", wire, n, ns, reply_op, send_keys, reply, reply_cap, reply_off, stream_reply, state, msgs,
+            count, info)
+        p = ctypes.c_void_p
+        rc = self._L.wsg_reply_checked(self._ctx, p(wire.data_ptr()), wire.numel(), p(frame_start.data_ptr()), n,
+                                       p(stream_first.data_ptr()), ns, p(state.data_ptr()), p(proto.data_ptr()),
+                                       int(role), int(max_message), p(also.data_ptr()) if also is not None else None,
+                                       rule, 1 if mask else 0,
+                                       p(send_keys.data_ptr()) if send_keys is not None else None,
+                                       p(reply.data_ptr()), cap, p(reply_off.data_ptr()), p(stream_reply.data_ptr()),
+                                       p(close_off.data_ptr()), p(verdict.data_ptr()), p(result.data_ptr()),
+                                       p(msgs.data_ptr()), p(count.data_ptr()), p(info.data_ptr()),
+                                       self._stream(stream))
+        _check(rc, "wsg_reply_checked")
+        return reply, reply_off, stream_reply, close_off, verdict, proto, result, msgs, count, state, info
+
+    def reply_checked_streams(self, wire, spans, proto=None, role=PROTO_ANY, max_message=0, reply_op=ECHO_REPLY,
+                              mask=False, send_keys=None, state=None, frame_start=None, frame_cap=None,
+                              stream_first=None, reply=None, reply_cap=None, stream=None, reply_off=None,
+                              stream_reply=None, close_off=None, verdict=None, result=None, msgs=None, count=None,
+                              info=None):
+        """wsg_reply_checked_streams: reply_streams with reply_checked in the
+        middle.  Returns reply_checked's tuple followed by (frame_start,
+        stream_first, n_frames)."""
+        ns, fcap, frame_start, stream_first = self._frame_args("reply_checked_streams", wire, spans, frame_start,
+                                                               frame_cap, stream_first)
+        proto, close_off, verdict, result, count = self._checked_args("reply_checked_streams", wire.device, ns, proto,
+                                                                      close_off, verdict, result, count)
+        rule, cap, reply, reply_off, stream_reply, state, msgs, count, info = self._reply_args(
+            "reply_checked_streams", wire, fcap, ns, reply_op, send_keys, reply, reply_cap, reply_off, stream_reply,
+            state, msgs, count, info)
+        n = ctypes.c_uint32()
+        p = ctypes.c_void_p
+        rc = self._L.wsg_reply_checked_streams(
+            self._ctx, p(wire.data_ptr()), wire.numel(), p(spans.data_ptr()), ns, p(state.data_ptr()),
+            p(frame_start.data_ptr()), fcap, p(stream_first.data_ptr()), p(proto.data_ptr()), int(role),
+            int(max_message), rule, 1 if mask else 0, p(send_keys.data_ptr()) if send_keys is not None else None,
+            p(reply.data_ptr()), cap, p(reply_off.data_ptr()), p(stream_reply.data_ptr()), p(close_off.data_ptr()),
+            p(verdict.data_ptr()), p(result.data_ptr()), p(msgs.data_ptr()), p(count.data_ptr()), p(info.data_ptr()),
+            ctypes.byref(n), self._stream(stream))
+        _check(rc, "wsg_reply_checked_streams")
+        return (reply, reply_off, stream_reply, close_off, verdict, proto, result, msgs, count, state, info,
+                frame_start, stream_first, n.value)
+
+    def utf8_verdicts(self, msgs, count, valid, n_streams, which=UTF8_TEXT | UTF8_CLOSE, msg_room=None, also=None,
+                      stream=None):
+        """wsg_utf8_verdicts: check_utf8's ``valid`` as reply_checked's
+        ``also``: PROTO_VERDICT bytes per stream, all 0xFF or {PV_UTF8, 1007,
+        the FIN frame of the stream's first invalid message}.  ``which`` as
+        given to check_utf8."""
+        t = self._torch
+        ns = int(n_streams)
+        if msg_room is None:
+            msg_room = min(int(msgs.numel()) // MSG.itemsize, int(valid.numel()))
+        room = int(msg_room)
+        if also is None:
+            also = t.empty(max(ns, 1) * PROTO_VERDICT.itemsize, dtype=t.uint8, device=msgs.device)
+        if (int(msgs.numel()) < room * MSG.itemsize or int(valid.numel()) < room or valid.element_size() != 8
+                or int(count.numel()) < 2 or count.element_size() != 8
+                or int(also.numel()) * also.element_size() < ns * PROTO_VERDICT.itemsize):
+            raise WSGError(WSG_EINVAL, "utf8_verdicts: a buffer is smaller than the batch needs")
+        p = ctypes.c_void_p
+        rc = self._L.wsg_utf8_verdicts(self._ctx, p(msgs.data_ptr()), p(count.data_ptr()), room, int(which),
+                                       p(valid.data_ptr()), ns, p(also.data_ptr()), self._stream(stream))
+        _check(rc, "wsg_utf8_verdicts")
+        return also
 
     def prepare_decode(self, wire, frame_start, out, info, stream=None):
         """wsg_decode_batch on fixed buffers (a server's batch arena), with

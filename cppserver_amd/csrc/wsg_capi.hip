@@ -1494,6 +1494,125 @@ int wsg_reply_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_
                         });
 }
 
+// wsg_reply_messages with wsg_check_protocol inside it: the protocol kernels
+// run on the d_info the plan's header pass has just written, and the reply
+// kernels stop every stream at its terminal frame and close it there.
+int wsg_reply_checked(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const uint64_t* d_frame_start, uint32_t n,
+                      const uint32_t* d_stream_first, uint32_t n_streams, wsg_stream_state* d_state,
+                      wsg_proto_state* d_proto, uint32_t role, uint64_t max_message, const wsg_proto_verdict* d_also,
+                      const uint8_t reply_op[5], int mask, const uint32_t* d_send_key, uint8_t* d_reply,
+                      uint64_t reply_cap, uint64_t* d_reply_off, uint64_t* d_stream_reply, uint64_t* d_close_off,
+                      wsg_proto_verdict* d_verdict, uint64_t* d_result, wsg_msg* d_msgs, uint64_t* d_count,
+                      wsg_recv_info* d_info, void* stream)
+{
+    if (!c || !d_count || !d_stream_first || !reply_op || !d_reply_off || !d_stream_reply || !d_close_off ||
+        !d_proto || !d_verdict || !d_result || (wire_len && !d_wire) || (reply_cap && !d_reply) ||
+        (n && (!d_frame_start || !d_info || !d_msgs || n_streams == 0)) || (n_streams && !d_state) ||
+        role > WSG_PROTO_CLIENT || n == UINT32_MAX || n_streams == UINT32_MAX)
+        return WSG_EINVAL;
+    if (!aligned16(d_wire) || !aligned16(d_reply))
+        return WSG_EINVAL;
+    if (!aligned8(d_frame_start) || (reinterpret_cast<uintptr_t>(d_stream_first) & 3u) || !aligned8(d_state) ||
+        !aligned8(d_proto) || !aligned8(d_also) || (reinterpret_cast<uintptr_t>(d_send_key) & 3u) ||
+        !aligned8(d_reply_off) || !aligned8(d_stream_reply) || !aligned8(d_close_off) || !aligned8(d_verdict) ||
+        !aligned8(d_result) || !aligned8(d_msgs) || !aligned8(d_count) || !aligned8(d_info))
+        return WSG_EINVAL;
+    if (c->check &&
+        (!in_alloc(d_wire, (wire_len + 15) & ~uint64_t(15)) || !in_alloc(d_frame_start, uint64_t(n) * 8) ||
+         !in_alloc(d_stream_first, (uint64_t(n_streams) + 1) * 4) ||
+         !in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) ||
+         !in_alloc(d_proto, uint64_t(n_streams) * sizeof(wsg_proto_state)) ||
+         (d_also && !in_alloc(d_also, uint64_t(n_streams) * sizeof(wsg_proto_verdict))) ||
+         (d_send_key && !in_alloc(d_send_key, uint64_t(n_streams) * 4)) || !in_alloc(d_reply, reply_cap) ||
+         !in_alloc(d_reply_off, (uint64_t(n) + 1) * 8) || !in_alloc(d_stream_reply, (uint64_t(n_streams) + 1) * 8) ||
+         !in_alloc(d_close_off, uint64_t(n_streams) * 8) ||
+         !in_alloc(d_verdict, uint64_t(n_streams) * sizeof(wsg_proto_verdict)) || !in_alloc(d_result, 3 * 8) ||
+         !in_alloc(d_msgs, uint64_t(n) * sizeof(wsg_msg)) || !in_alloc(d_count, 5 * 8) ||
+         !in_alloc(d_info, uint64_t(n) * sizeof(wsg_recv_info))))
+        return WSG_EINVAL;
+    hipStream_t s = pick(c, stream);
+    wsg::ReplyRule rule;
+    for (int k = 0; k < 5; ++k)
+        rule.op[k] = reply_op[k];
+    rule.mask = mask ? 1 : 0;
+    if (int rc = ensure_array(c->d_proto_plan, c->proto_plan_cap, wsg::proto_plan_layout(nullptr, n, n_streams, nullptr)))
+        return rc;
+    wsg::ProtoPlan pplan;
+    wsg::proto_plan_layout(c->d_proto_plan, n, n_streams, &pplan);
+    // both scratches are the context's: behind the last user of either,
+    // whatever stream it ran on
+    wsg::MsgPlan plan;
+    uint64_t pieces_cap;
+    bool ordered = false, pordered = false;
+    if (int rc = msg_scratch(c, s, n, wire_len, &plan, &pieces_cap, &ordered))
+        return rc;
+    if (int rc = scratch_enter(c->proto_order, s, &pordered))
+        return rc;
+    WSG_HIP(wsg::launch_reply_checked_plan(s, grid_for(c, ceil_div(n_streams, wsg::BLOCK)), d_wire, wire_len,
+                                           d_frame_start, n, d_stream_first, n_streams, d_state, d_proto, role,
+                                           max_message, d_also, rule, d_send_key, d_reply, reply_cap, d_reply_off,
+                                           d_stream_reply, d_close_off, d_verdict, d_result, d_msgs, d_count, d_info,
+                                           plan, pplan, c->d_msg_pieces, pieces_cap, c->d_err));
+    if (n) {
+        const int t = timing_begin(c, s);
+        WSG_HIP(wsg::launch_reply_gather(s, grid_for(c, ceil_div(pieces_cap, wsg::BLOCK / 64), c->enc_blocks_per_cu),
+                                         d_wire, plan, c->d_msg_pieces, pieces_cap, d_reply, reply_cap));
+        timing_end(c, s, t);
+    }
+    if (int rc = scratch_leave(c->proto_order, s, pordered))
+        return rc;
+    return scratch_leave(c->msg_order, s, ordered);
+}
+
+int wsg_reply_checked_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_stream_span* d_span,
+                              uint32_t n_streams, wsg_stream_state* d_state, uint64_t* d_frame_start,
+                              uint32_t frame_cap, uint32_t* d_stream_first, wsg_proto_state* d_proto, uint32_t role,
+                              uint64_t max_message, const uint8_t reply_op[5], int mask, const uint32_t* d_send_key,
+                              uint8_t* d_reply, uint64_t reply_cap, uint64_t* d_reply_off, uint64_t* d_stream_reply,
+                              uint64_t* d_close_off, wsg_proto_verdict* d_verdict, uint64_t* d_result, wsg_msg* d_msgs,
+                              uint64_t* d_count, wsg_recv_info* d_info, uint32_t* n_frames_out, void* stream)
+{
+    if (!c || !n_frames_out || !d_count || !reply_op || !d_reply_off || !d_stream_reply || !d_close_off || !d_proto ||
+        !d_verdict || !d_result || (n_streams && !d_state) || (reply_cap && !d_reply) ||
+        (frame_cap && (!d_msgs || !d_info)) || !aligned16(d_reply) || role > WSG_PROTO_CLIENT)
+        return WSG_EINVAL;
+    if (c->check &&
+        (!in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) || !in_alloc(d_reply, reply_cap) ||
+         !in_alloc(d_reply_off, (uint64_t(frame_cap) + 1) * 8) ||
+         !in_alloc(d_msgs, uint64_t(frame_cap) * sizeof(wsg_msg)) ||
+         !in_alloc(d_info, uint64_t(frame_cap) * sizeof(wsg_recv_info))))
+        return WSG_EINVAL;
+    return streams_then(c, d_wire, wire_len, d_span, n_streams, d_state, d_frame_start, frame_cap, d_stream_first,
+                        d_count, n_frames_out, stream, [&](uint32_t n) {
+                            return wsg_reply_checked(c, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams,
+                                                     d_state, d_proto, role, max_message, nullptr, reply_op, mask,
+                                                     d_send_key, d_reply, reply_cap, d_reply_off, d_stream_reply,
+                                                     d_close_off, d_verdict, d_result, d_msgs, d_count, d_info,
+                                                     stream);
+                        });
+}
+
+// wsg_check_utf8's d_valid as the d_also of wsg_reply_checked: a seed per
+// stream, then one lane per record.
+int wsg_utf8_verdicts(wsg_ctx* c, const wsg_msg* d_msgs, const uint64_t* d_count, uint32_t msg_room, uint32_t which,
+                      const uint64_t* d_valid, uint32_t n_streams, wsg_proto_verdict* d_also, void* stream)
+{
+    if (!c || !d_count || (msg_room && (!d_msgs || !d_valid)) || (n_streams && !d_also) || n_streams == UINT32_MAX)
+        return WSG_EINVAL;
+    if (!aligned8(d_msgs) || !aligned8(d_count) || !aligned8(d_valid) || !aligned8(d_also))
+        return WSG_EINVAL;
+    if (c->check && (!in_alloc(d_msgs, uint64_t(msg_room) * sizeof(wsg_msg)) ||
+                     !in_alloc(d_valid, uint64_t(msg_room) * 8) || !in_alloc(d_count, 2 * 8) ||
+                     !in_alloc(d_also, uint64_t(n_streams) * sizeof(wsg_proto_verdict))))
+        return WSG_EINVAL;
+    if (n_streams == 0)
+        return WSG_OK;
+    WSG_HIP(wsg::launch_utf8_verdicts(pick(c, stream), grid_for(c, ceil_div(msg_room, wsg::BLOCK)),
+                                      grid_for(c, ceil_div(n_streams, wsg::BLOCK)), d_msgs, d_count, msg_room, which,
+                                      d_valid, n_streams, d_also));
+    return WSG_OK;
+}
+
 namespace {
 
 // Small-frame batches (average frame <= small_avg) take k_encode_small,

@@ -140,6 +140,23 @@ hipError_t launch_reply_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_l
                              uint64_t* reply_off, uint64_t* stream_reply, wsg_msg* msgs, uint64_t* count,
                              wsg_recv_info* info, const MsgPlan& plan, MsgPiece* pieces, uint64_t pieces_cap,
                              unsigned long long* err);
+// wsg_reply_checked's plan pass: launch_reply_plan with the protocol kernels
+// (launch_proto_* below, d_state's consumed written ahead of them) and the
+// merge with `also` (or null) between the message plan and the reply kernels,
+// whose checked instantiations stop every stream's replies at its terminal
+// frame and put its close frame there; d_close_off, d_verdict, d_proto,
+// d_result and d_count[0..5) besides launch_reply_plan's outputs.
+// stream_grid: blocks of the per-stream kernels (grid-stride).
+struct ProtoPlan;
+hipError_t launch_reply_checked_plan(hipStream_t s, int stream_grid, const uint8_t* wire, uint64_t wire_len,
+                                     const uint64_t* fs, uint32_t n, const uint32_t* stream_first, uint32_t n_streams,
+                                     wsg_stream_state* state, wsg_proto_state* proto, uint32_t role,
+                                     uint64_t max_message, const wsg_proto_verdict* also, const ReplyRule& rule,
+                                     const uint32_t* send_key, uint8_t* reply, uint64_t reply_cap, uint64_t* reply_off,
+                                     uint64_t* stream_reply, uint64_t* close_off, wsg_proto_verdict* verdict,
+                                     uint64_t* result, wsg_msg* msgs, uint64_t* count, wsg_recv_info* info,
+                                     const MsgPlan& plan, const ProtoPlan& pplan, MsgPiece* pieces,
+                                     uint64_t pieces_cap, unsigned long long* err);
 // k_msg_gather over those records: every replied payload byte, re-keyed, to its place in reply.
 hipError_t launch_reply_gather(hipStream_t s, int grid, const uint8_t* wire, const MsgPlan& plan,
                                const MsgPiece* pieces, uint64_t pieces_cap, uint8_t* reply, uint64_t reply_cap);
@@ -184,6 +201,12 @@ hipError_t launch_utf8_scan(hipStream_t s, int grid, const uint8_t* msg, uint64_
 hipError_t launch_utf8_count(hipStream_t s, int grid, const wsg_msg* msgs, const uint64_t* count, uint32_t msg_room,
                              uint64_t msg_cap, uint32_t which, const uint64_t* valid, uint64_t* result);
 
+// wsg_utf8_verdicts: also[j] all 0xFF, then the lowest {WSG_PV_UTF8, 1007,
+// FIN frame} over stream j's selected records with d_valid[m] < len.
+hipError_t launch_utf8_verdicts(hipStream_t s, int rec_grid, int stream_grid, const wsg_msg* msgs,
+                                const uint64_t* count, uint32_t msg_room, uint32_t which, const uint64_t* valid,
+                                uint32_t n_streams, wsg_proto_verdict* also);
+
 // ---- protocol rules on the device (wsg_check_protocol; wsg_proto.hip) -------
 struct ProtoStep;   // wsg_proto.h
 // Scratch of one call, carved by the host out of one device block
@@ -209,6 +232,9 @@ hipError_t launch_proto_judge(hipStream_t s, const uint8_t* wire, uint64_t wire_
                               uint32_t n, const uint32_t* stream_first, const wsg_stream_state* state,
                               const wsg_proto_state* proto, uint32_t role, uint64_t max_message, const ProtoPlan& plan,
                               wsg_proto_verdict* verdict);
+// wsg_reply_checked: d_verdict[j] replaced by also[j] where that comes first (one lane per stream, grid-stride).
+hipError_t launch_proto_merge(hipStream_t s, int grid, uint32_t n, const uint32_t* stream_first, uint32_t n_streams,
+                              const wsg_proto_verdict* also, wsg_proto_verdict* verdict);
 // One lane per stream (grid-stride): d_proto and d_result's counts.
 hipError_t launch_proto_finish(hipStream_t s, int grid, uint32_t n, const uint32_t* stream_first, uint32_t n_streams,
                                const wsg_stream_state* state, wsg_proto_state* proto, const ProtoPlan& plan,

@@ -1,6 +1,6 @@
 // wsg_messages.hip — message assembly and replies on the device
-// (wsg_decode_messages, wsg_reply_messages): the plan kernels, k_msg_gather
-// and their launchers.
+// (wsg_decode_messages, wsg_reply_messages, wsg_reply_checked): the plan
+// kernels, k_msg_gather and their launchers.
 #include "wsg_device.h"
 
 namespace wsg {
@@ -302,6 +302,27 @@ __global__ __launch_bounds__(BLOCK) void k_msg_state(const wsg_recv_info* __rest
     *reinterpret_cast<uint64_t*>(state + j) = uint64_t(consumed) | (uint64_t(op & 0xFFu) << 32);
 }
 
+// wsg_reply_checked: d_state[j].consumed alone, behind k_msg_scan_blocks: the
+// protocol judge reads it, and k_msg_state, which writes the same value
+// beside the opcode, has to stay behind the reply kernels (they read the
+// opcode's seed).
+__global__ __launch_bounds__(BLOCK) void k_msg_consumed(uint32_t n, const uint32_t* __restrict__ sf, uint32_t ns,
+                                                        wsg_stream_state* state, MsgPlan P)
+{
+    const uint64_t j64 = uint64_t(blockIdx.x) * BLOCK + threadIdx.x;
+    if (j64 >= ns)
+        return;
+    const uint32_t j = uint32_t(j64);
+    const uint32_t start = min(sf[j], n), end = max(min(sf[j + 1], n), start);
+    uint32_t consumed = 0;
+    if (fins_before(P, n, end) > fins_before(P, n, start)) {
+        const uint32_t last = last_fin_before(P, n, end);   // + 1: in (start, end]
+        if (last > start && last <= end)
+            consumed = last - start;
+    }
+    state[j].consumed = consumed;
+}
+
 // ---- replies (wsg_reply_messages) -------------------------------------------
 // The plan above up to k_msg_bytes_blocks, then, one lane per frame again:
 //   k_reply_local     FIN lanes write their wsg_msg and size the reply frame
@@ -317,6 +338,12 @@ __global__ __launch_bounds__(BLOCK) void k_msg_state(const wsg_recv_info* __rest
 //                     phase; a lane per stream: d_stream_reply
 // and k_msg_gather over those records: every payload byte is read once from
 // the received wire and written once, re-keyed, into its reply frame.
+// wsg_reply_checked runs the CHECKED instantiations of the three behind the
+// protocol kernels (wsg_proto.hip): every frame lane reads its stream's
+// effective verdict through P.sidx, a reply is sized only in front of the
+// terminal frame t, lane t sizes and writes the stream's close frame, and the
+// per-stream lanes write d_close_off.  The close frame belongs to frame t as a
+// reply belongs to its FIN frame, so one scan places both.
 
 namespace {
 
@@ -353,25 +380,69 @@ __device__ __forceinline__ uint64_t reply_before(const MsgPlan& P, uint32_t n, u
     return k < n ? P.rex[k] + P.brep_pre[k / BLOCK] : P.rtot[2];
 }
 
+// ---- wsg_reply_checked: a stream's effective verdict, as the reply kernels read it
+// (one little-endian word: code, pad, status, the terminal frame on top; all
+// 0xFF: none, and then no frame index equals or exceeds its frame).
+__device__ __forceinline__ uint32_t verdict_frame(uint64_t v) { return uint32_t(v >> 32); }
+
+// The close frame a verdict is answered with: PrepareSendFrame(WSG_FIN | WSG_CLOSE,
+// mask, NULL, 0, status); 1005 never goes on the wire (RFC 6455 7.4.1).
+__device__ __forceinline__ int32_t close_status(uint64_t v)
+{
+    const int32_t s = int32_t((v >> 16) & 0xFFFFu);
+    return s == 1005 ? 1000 : s;
+}
+
+__device__ __forceinline__ uint64_t close_size(const ReplyRule& rule, uint64_t v)
+{
+    const SendGeom g = send_geom(uint8_t(WSG_FIN | WSG_CLOSE), rule.mask != 0, 0, close_status(v));
+    return g.hdr + g.body;
+}
+
 } // namespace
 
+// CHECKED (wsg_reply_checked): frame i sizes its reply only in front of its
+// stream's terminal frame t, and the close frame's size when i == t; the
+// block sum of reply frames carries the close frames in its upper half too.
+// (Kernel templates, not a shared body: the rule stays a kernel argument,
+// whose bytes are indexed where they lie; a copy of it would live in scratch.)
+template <bool CHECKED>
 __global__ __launch_bounds__(BLOCK) void k_reply_local(const uint8_t* __restrict__ wire,
                                                        const wsg_recv_info* __restrict__ info, uint32_t n,
                                                        const uint32_t* __restrict__ sf,
                                                        const wsg_stream_state* __restrict__ state, MsgPlan P,
-                                                       ReplyRule rule, wsg_msg* __restrict__ msgs)
+                                                       ReplyRule rule, wsg_msg* __restrict__ msgs,
+                                                       const uint64_t* __restrict__ verdict)
 {
     const uint64_t i64 = uint64_t(blockIdx.x) * BLOCK + threadIdx.x;
     const uint32_t i = uint32_t(i64);
-    uint64_t size = 0;
-    if (i64 < n && info[i].fin) {
-        const MsgRec m = msg_at_fin(wire, info, n, sf, state, P, i, info[i].len);
-        put_msg(msgs + fins_before(P, n, i), m, i);
-        size = reply_size(rule, reply_of(rule, m.kind, m.op, m.len, m.status));
+    uint64_t size = 0, frames = 0;
+    if (CHECKED) {
+        if (i64 < n) {
+            const uint64_t v = verdict[P.sidx[i]];
+            if (info[i].fin) {   // every record is written, answered or not
+                const MsgRec m = msg_at_fin(wire, info, n, sf, state, P, i, info[i].len);
+                put_msg(msgs + fins_before(P, n, i), m, i);
+                if (i < verdict_frame(v))
+                    size = reply_size(rule, reply_of(rule, m.kind, m.op, m.len, m.status));
+            }
+            frames = size != 0;
+            if (i == verdict_frame(v)) {   // (and then size == 0)
+                size = close_size(rule, v);
+                frames = 1 | (1ull << 32);
+            }
+        }
+    } else {
+        if (i64 < n && info[i].fin) {
+            const MsgRec m = msg_at_fin(wire, info, n, sf, state, P, i, info[i].len);
+            put_msg(msgs + fins_before(P, n, i), m, i);
+            size = reply_size(rule, reply_of(rule, m.kind, m.op, m.len, m.status));
+        }
+        frames = size != 0;
     }
     uint64_t tb, tn;
     const uint64_t eb = block_scan_ex(size, OpAdd{}, &tb);
-    block_scan_ex(uint64_t(size != 0), OpAdd{}, &tn);
+    block_scan_ex(frames, OpAdd{}, &tn);
     if (i64 < n)
         P.rex[i] = eb;
     if (threadIdx.x == 0) {
@@ -380,8 +451,9 @@ __global__ __launch_bounds__(BLOCK) void k_reply_local(const uint8_t* __restrict
     }
 }
 
+template <bool CHECKED>
 __global__ __launch_bounds__(BLOCK) void k_reply_blocks(MsgPlan P, uint32_t nb, uint32_t n, uint64_t reply_cap,
-                                                        uint64_t* __restrict__ count, unsigned long long* err)
+                                             uint64_t* __restrict__ count, unsigned long long* err)
 {
     const uint64_t cb = scan_partials(P.brep, P.brep_pre, nb, OpAdd{});
     const uint64_t cn = scan_partials<uint64_t>(P.brn, nullptr, nb, OpAdd{});
@@ -389,27 +461,36 @@ __global__ __launch_bounds__(BLOCK) void k_reply_blocks(MsgPlan P, uint32_t nb, 
         P.rtot[2] = cb;         // k_msg_gather's view of the totals: bytes against the capacity,
         P.rtot[3] = P.tot[3];   // and the piece count
         count[2] = cb;
-        count[3] = cn;
+        if (CHECKED) {          // (frames <= n < 2^32: the halves do not meet)
+            count[3] = uint32_t(cn);
+            count[4] = cn >> 32;
+        } else {
+            count[3] = cn;
+        }
         if (cb > reply_cap)   // behind every frame error: the latch keeps the smallest
             latch(err, n, WSG_ENOMEM);
     }
 }
 
-__global__ __launch_bounds__(BLOCK) void k_reply_finalize(const wsg_recv_info* __restrict__ info, uint32_t n,
-                                                          const uint32_t* __restrict__ sf, uint32_t ns, MsgPlan P,
-                                                          ReplyRule rule, const uint32_t* __restrict__ send_key,
-                                                          const wsg_msg* __restrict__ msgs,
-                                                          uint8_t* __restrict__ reply, uint64_t reply_cap,
-                                                          uint64_t* __restrict__ reply_off,
-                                                          uint64_t* __restrict__ stream_reply,
-                                                          MsgPiece* __restrict__ pieces, uint64_t pieces_cap)
+template <bool CHECKED>
+__global__ __launch_bounds__(BLOCK) void k_reply_finalize(
+    const wsg_recv_info* __restrict__ info, uint32_t n, const uint32_t* __restrict__ sf, uint32_t ns, MsgPlan P,
+    ReplyRule rule, const uint32_t* __restrict__ send_key, const wsg_msg* __restrict__ msgs,
+    uint8_t* __restrict__ reply, uint64_t reply_cap, uint64_t* __restrict__ reply_off,
+    uint64_t* __restrict__ stream_reply, MsgPiece* __restrict__ pieces, uint64_t pieces_cap,
+    const uint64_t* __restrict__ verdict, uint64_t* __restrict__ close_off)
 {
     const uint64_t i64 = uint64_t(blockIdx.x) * BLOCK + threadIdx.x;
     const uint32_t i = uint32_t(i64);
     const uint64_t total = P.rtot[2], nmsg = P.tot[0];
     // connection j's replies start where its first message's does
-    for (uint64_t j = i64; j <= ns; j += uint64_t(gridDim.x) * BLOCK)
+    for (uint64_t j = i64; j <= ns; j += uint64_t(gridDim.x) * BLOCK) {
         stream_reply[j] = reply_before(P, n, min(sf[j], n));
+        if (CHECKED && j < ns) {   // its close frame belongs to the terminal frame, which holds no reply
+            const uint32_t t = verdict_frame(verdict[j]);
+            close_off[j] = t < n && P.sidx[t] == uint32_t(j) ? reply_before(P, n, t) : UINT64_MAX;
+        }
+    }
     if (i64 == 0)
         reply_off[nmsg] = total;
     uint64_t lo = 0, hi = 0, poff = 0, d0 = 0, plen = 0;
@@ -418,9 +499,26 @@ __global__ __launch_bounds__(BLOCK) void k_reply_finalize(const wsg_recv_info* _
         piece_range(pieces_before(P, n, i), pieces_before(P, n, i + 1), pieces_cap, lo, hi);
         const wsg_recv_info r = info[i];
         const uint64_t m = fins_before(P, n, i);
+        if (CHECKED) {
+            const uint32_t j = P.sidx[i];
+            const uint64_t v = verdict[j];
+            if (i == verdict_frame(v) && total <= reply_cap) {   // the terminal frame's lane: the close frame
+                const uint64_t at = reply_before(P, n, i);
+                const FrameRec R = make_rec(at, nullptr, 0, send_key ? send_key[j] : 0u, close_status(v),
+                                            uint8_t(WSG_FIN | WSG_CLOSE), rule.mask != 0);
+                const v4u h = frame_head(R);
+                for (uint32_t t = 0; t < R.hdr + R.prefix; ++t)
+                    reply[at + t] = uint8_t(lane_byte(h, t));
+            }
+        }
         if ((r.fin || hi > lo) && m < nmsg) {   // frame i belongs to message m
             const MsgRec mr = get_msg(msgs + m);
-            const ReplyOf a = reply_of(rule, mr.kind, mr.op, mr.len, mr.status);
+            ReplyOf a = reply_of(rule, mr.kind, mr.op, mr.len, mr.status);
+            if (CHECKED) {   // k_reply_local's decision, taken at the message's FIN frame
+                const uint32_t nframes = uint32_t(reinterpret_cast<const uint64_t*>(msgs + m)[3]);
+                if (mr.first + nframes - 1 >= verdict_frame(verdict[mr.stream]))
+                    a.op = 0;
+            }
             const uint64_t at = reply_before(P, n, i);
             const uint32_t skey = send_key ? send_key[mr.stream] : 0u;
             if (r.fin)
@@ -662,12 +760,64 @@ hipError_t launch_reply_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_l
     // (no d_msg: its size, d_count[1], meets no capacity)
     return launch_plan(s, wire, wire_len, fs, n, stream_first, n_streams, state, UINT64_MAX, count, 4, info, plan, err,
                        [&](uint32_t nb) {
-                           k_reply_local<<<nb, BLOCK, 0, s>>>(wire, info, n, stream_first, state, plan, rule, msgs);
-                           k_reply_blocks<<<1, BLOCK, 0, s>>>(plan, nb, n, reply_cap, count, err);
-                           k_reply_finalize<<<nb, BLOCK, 0, s>>>(info, n, stream_first, n_streams, plan, rule, send_key,
-                                                                 msgs, reply, reply_cap, reply_off, stream_reply,
-                                                                 pieces, pieces_cap);
+                           k_reply_local<false><<<nb, BLOCK, 0, s>>>(wire, info, n, stream_first, state, plan, rule,
+                                                                     msgs, nullptr);
+                           k_reply_blocks<false><<<1, BLOCK, 0, s>>>(plan, nb, n, reply_cap, count, err);
+                           k_reply_finalize<false><<<nb, BLOCK, 0, s>>>(info, n, stream_first, n_streams, plan, rule,
+                                                                        send_key, msgs, reply, reply_cap, reply_off,
+                                                                        stream_reply, pieces, pieces_cap, nullptr,
+                                                                        nullptr);
                        });
+}
+
+hipError_t launch_reply_checked_plan(hipStream_t s, int stream_grid, const uint8_t* wire, uint64_t wire_len,
+                                     const uint64_t* fs, uint32_t n, const uint32_t* stream_first, uint32_t n_streams,
+                                     wsg_stream_state* state, wsg_proto_state* proto, uint32_t role,
+                                     uint64_t max_message, const wsg_proto_verdict* also, const ReplyRule& rule,
+                                     const uint32_t* send_key, uint8_t* reply, uint64_t reply_cap, uint64_t* reply_off,
+                                     uint64_t* stream_reply, uint64_t* close_off, wsg_proto_verdict* verdict,
+                                     uint64_t* result, wsg_msg* msgs, uint64_t* count, wsg_recv_info* info,
+                                     const MsgPlan& plan, const ProtoPlan& pplan, MsgPiece* pieces,
+                                     uint64_t pieces_cap, unsigned long long* err)
+{
+    hipError_t pe = hipSuccess;   // of the protocol launchers (each has taken its launch's error)
+    const auto keep = [&pe](hipError_t e) {
+        if (pe == hipSuccess)
+            pe = e;
+    };
+    if (n == 0) {   // no reply, no close frame, nothing judged: the seeds, and d_proto as it came
+        if (hipError_t e = hipMemsetAsync(plan.rtot, 0, 4 * sizeof(uint64_t), s); e != hipSuccess)
+            return e;
+        if (hipError_t e = hipMemsetAsync(reply_off, 0, sizeof(uint64_t), s); e != hipSuccess)
+            return e;
+        if (hipError_t e = hipMemsetAsync(stream_reply, 0, (uint64_t(n_streams) + 1) * sizeof(uint64_t), s);
+            e != hipSuccess)
+            return e;
+        if (n_streams)
+            if (hipError_t e = hipMemsetAsync(close_off, 0xFF, uint64_t(n_streams) * sizeof(uint64_t), s);
+                e != hipSuccess)
+                return e;
+        keep(launch_proto_scan(s, info, n, stream_first, n_streams, proto, pplan, verdict, result));
+        keep(launch_proto_finish(s, stream_grid, n, stream_first, n_streams, state, proto, pplan, verdict, result));
+    }
+    const hipError_t e = launch_plan(
+        s, wire, wire_len, fs, n, stream_first, n_streams, state, UINT64_MAX, count, 5, info, plan, err,
+        [&](uint32_t nb) {   // (n > 0, so n_streams > 0: the caller checks)
+            const uint64_t* v = reinterpret_cast<const uint64_t*>(verdict);
+            k_msg_consumed<<<(n_streams + BLOCK - 1) / BLOCK, BLOCK, 0, s>>>(n, stream_first, n_streams, state, plan);
+            keep(launch_proto_scan(s, info, n, stream_first, n_streams, proto, pplan, verdict, result));
+            keep(launch_proto_judge(s, wire, wire_len, info, n, stream_first, state, proto, role, max_message, pplan,
+                                    verdict));
+            if (also)
+                keep(launch_proto_merge(s, stream_grid, n, stream_first, n_streams, also, verdict));
+            keep(launch_proto_finish(s, stream_grid, n, stream_first, n_streams, state, proto, pplan, verdict, result));
+            k_reply_local<true><<<nb, BLOCK, 0, s>>>(wire, info, n, stream_first, state, plan, rule, msgs, v);
+            k_reply_blocks<true><<<1, BLOCK, 0, s>>>(plan, nb, n, reply_cap, count, err);
+            k_reply_finalize<true><<<nb, BLOCK, 0, s>>>(info, n, stream_first, n_streams, plan, rule, send_key, msgs,
+                                                          reply, reply_cap, reply_off, stream_reply, pieces,
+                                                          pieces_cap, v, close_off);
+        });
+    return pe != hipSuccess ? pe : e;
 }
 
 hipError_t launch_reply_gather(hipStream_t s, int grid, const uint8_t* wire, const MsgPlan& plan,

@@ -28,6 +28,8 @@ namespace wsg {
 //                   read by the two frame kernels, so none of them writes it),
 //                   and d_result's counts, one atomic of each per wave that
 //                   has something to add
+//   k_proto_merge   wsg_reply_checked with d_also only, in front of the finish:
+//                   one lane per stream, the other verdict where it comes first
 // Work is proportional to frames plus streams; no lane walks a stream.
 
 namespace {
@@ -209,6 +211,28 @@ __global__ __launch_bounds__(BLOCK) void k_proto_finish(uint32_t n, const uint32
         atomicAdd(result + 2, static_cast<unsigned long long>(closed));
 }
 
+// wsg_reply_checked's merge, one lane per stream between the judge and
+// k_proto_finish (so that d_result counts what it leaves): d_verdict[j]
+// becomes the caller's other verdict when that names a frame of the stream
+// and comes first: a lower frame, or the same frame where the protocol's is a
+// clean close and the other a violation.  All 0xFF in `also`: none.
+__global__ __launch_bounds__(BLOCK) void k_proto_merge(uint32_t n, const uint32_t* __restrict__ sf, uint32_t ns,
+                                                       const uint64_t* __restrict__ also, uint64_t* verdict)
+{
+    for (uint64_t j = uint64_t(blockIdx.x) * BLOCK + threadIdx.x; j < ns; j += uint64_t(gridDim.x) * BLOCK) {
+        const uint64_t a = also[j];
+        const uint32_t frame = uint32_t(a >> 32);
+        const uint32_t start = min(sf[j], n), end = max(min(sf[j + 1], n), start);
+        if (a == UINT64_MAX || frame < start || frame >= end)
+            continue;
+        const uint64_t v = verdict[j];   // (all 0xFF: frame UINT32_MAX, behind every frame)
+        const uint32_t vf = uint32_t(v >> 32);
+        const uint32_t vcode = uint32_t(v) & 0xFFu, acode = uint32_t(a) & 0xFFu;
+        if (frame < vf || (frame == vf && vcode == WSG_PV_CLOSED && acode >= WSG_PV_FRAME))
+            verdict[j] = a;
+    }
+}
+
 uint64_t proto_plan_layout(uint8_t* base, uint32_t n, uint32_t ns, ProtoPlan* plan)
 {
     const uint64_t nb = (uint64_t(n) + BLOCK - 1) / BLOCK;
@@ -246,6 +270,14 @@ hipError_t launch_proto_judge(hipStream_t s, const uint8_t* wire, uint64_t wire_
     const uint32_t nb = uint32_t((uint64_t(n) + BLOCK - 1) / BLOCK);
     k_proto_judge<<<nb, BLOCK, 0, s>>>(wire, wire_len, info, n, stream_first, state, proto, role, max_message, plan,
                                        reinterpret_cast<unsigned long long*>(verdict));
+    return hipGetLastError();
+}
+
+hipError_t launch_proto_merge(hipStream_t s, int grid, uint32_t n, const uint32_t* stream_first, uint32_t n_streams,
+                              const wsg_proto_verdict* also, wsg_proto_verdict* verdict)
+{
+    k_proto_merge<<<grid, BLOCK, 0, s>>>(n, stream_first, n_streams, reinterpret_cast<const uint64_t*>(also),
+                                         reinterpret_cast<uint64_t*>(verdict));
     return hipGetLastError();
 }
 

@@ -249,6 +249,45 @@ __global__ __launch_bounds__(BLOCK) void k_utf8_count(const wsg_msg* __restrict_
     }
 }
 
+// wsg_utf8_verdicts: d_valid as verdicts wsg_reply_checked takes.  The seed,
+// one lane per stream, and, behind a kernel boundary, one lane per record: a
+// selected message with d_valid[m] < len fails its stream with 1007 at its
+// FIN frame; the stream's first one wins (the verdict word orders by frame).
+// Valid traffic issues no atomic.
+__global__ __launch_bounds__(BLOCK) void k_utf8_verdict_seed(uint32_t ns, unsigned long long* __restrict__ also)
+{
+    for (uint64_t j = uint64_t(blockIdx.x) * BLOCK + threadIdx.x; j < ns; j += uint64_t(gridDim.x) * BLOCK)
+        also[j] = ~0ull;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_utf8_verdicts(const wsg_msg* __restrict__ msgs,
+                                                         const uint64_t* __restrict__ count, uint32_t msg_room,
+                                                         uint32_t which, const uint64_t* __restrict__ valid,
+                                                         uint32_t ns, unsigned long long* __restrict__ also)
+{
+    const uint64_t M = min(count[0], uint64_t(msg_room));
+    for (uint64_t m = uint64_t(blockIdx.x) * BLOCK + threadIdx.x; m < M; m += uint64_t(gridDim.x) * BLOCK) {
+        const Utf8Rec r = utf8_rec(msgs, uint32_t(m), which);
+        if (!r.selected || valid[m] >= r.len)
+            continue;
+        const uint64_t* w = reinterpret_cast<const uint64_t*>(msgs + m);
+        const uint32_t stream = uint32_t(w[2]), first = uint32_t(w[2] >> 32), nframes = uint32_t(w[3]);
+        if (stream < ns)   // (a table that is not this batch's: never a store outside d_also)
+            atomicMin(also + stream, uint64_t(WSG_PV_UTF8) | (1007ull << 16) | (uint64_t(first + nframes - 1) << 32));
+    }
+}
+
+hipError_t launch_utf8_verdicts(hipStream_t s, int rec_grid, int stream_grid, const wsg_msg* msgs,
+                                const uint64_t* count, uint32_t msg_room, uint32_t which, const uint64_t* valid,
+                                uint32_t n_streams, wsg_proto_verdict* also)
+{
+    unsigned long long* a = reinterpret_cast<unsigned long long*>(also);
+    k_utf8_verdict_seed<<<stream_grid, BLOCK, 0, s>>>(n_streams, a);
+    if (msg_room && n_streams)
+        k_utf8_verdicts<<<rec_grid, BLOCK, 0, s>>>(msgs, count, msg_room, which, valid, n_streams, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_utf8_init(hipStream_t s, int grid, const wsg_msg* msgs, const uint64_t* count, uint32_t msg_room,
                             uint64_t* valid, uint64_t* result)
 {

@@ -2,7 +2,8 @@
 
 numpy structured dtypes whose byte layout is exactly ``wsg_send_desc``,
 ``wsg_recv_info``, ``wsg_msg``, ``wsg_stream_state``, ``wsg_stream_span``,
-``wsg_proto_state`` and ``wsg_proto_verdict``;
+``wsg_proto_state`` and ``wsg_proto_verdict``, and the plans of the device
+entry points restated on the host;
 importing this module loads no native code.
 """
 import numpy as np
@@ -452,3 +453,103 @@ def protocol_plan(info, stream_first, proto_in, role, max_message, wire, consume
         result[1] = int(streams[bad].min())
     result[2] = int((verdict["code"][streams] == PV_CLOSED).sum())
     return verdict, proto_out, result
+
+
+# wsg_reply_checked / wsg_utf8_verdicts (include/wsg_capi.h).
+PV_UTF8 = 13
+NO_VERDICT = np.frombuffer(b"\xff" * 8, dtype=PROTO_VERDICT)[0]
+
+
+def _verdict_words(verdict):
+    """PROTO_VERDICT records as the little-endian words the kernels order them by."""
+    return np.ascontiguousarray(np.asarray(verdict, dtype=PROTO_VERDICT)).view("<u8").copy()
+
+
+def merge_verdicts(verdict, also, stream_first):
+    """wsg_reply_checked's effective verdicts: ``verdict`` (the protocol's,
+    PROTO_VERDICT per stream) with ``also`` (None: none) taken where it names
+    a frame of its stream [stream_first[j], stream_first[j+1]) and comes
+    first: a lower frame, or the same frame where the protocol's code is
+    PV_CLOSED and the other's >= 2.  An all-0xFF entry means none."""
+    out = np.array(np.asarray(verdict, dtype=PROTO_VERDICT), copy=True)
+    if also is None or len(out) == 0:
+        return out
+    also = np.asarray(also, dtype=PROTO_VERDICT)
+    sf = np.asarray(stream_first, dtype=np.int64)
+    a, v = _verdict_words(also), _verdict_words(out)
+    frame = also["frame"].astype(np.int64)
+    usable = (a != U64_MAX) & (frame >= sf[:-1]) & (frame < sf[1:])
+    vf = out["frame"].astype(np.int64)
+    take = usable & ((frame < vf) | ((frame == vf) & (out["code"] == PV_CLOSED) & (also["code"] >= PV_FRAME)))
+    v[take] = a[take]
+    return v.view(PROTO_VERDICT)
+
+
+def utf8_verdicts(msgs, valid, which, n_streams):
+    """wsg_utf8_verdicts: per stream, all 0xFF or {PV_UTF8, 1007, the FIN
+    frame} of its first message that ``which`` selects (utf8_plan's rule)
+    and whose valid[m] < len."""
+    msgs = np.asarray(msgs, dtype=MSG)
+    words = np.full(n_streams, U64_MAX, dtype=np.uint64)
+    kind, opcode = msgs["kind"], msgs["opcode"]
+    selected = np.full(len(msgs), bool(which & UTF8_EVERY))
+    if which & UTF8_TEXT:
+        selected |= (kind == CB_RECEIVED) & (opcode == WS_TEXT)
+    if which & UTF8_CLOSE:
+        selected |= kind == CB_CLOSE
+    bad = selected & (np.asarray(valid, dtype=np.uint64)[: len(msgs)] < msgs["len"]) & (msgs["stream"] < n_streams)
+    fin = msgs["first_frame"].astype(np.uint64) + msgs["nframes"].astype(np.uint64) - np.uint64(1)
+    word = np.uint64(PV_UTF8) | (np.uint64(1007) << np.uint64(16)) | (fin << np.uint64(32))
+    np.minimum.at(words, msgs["stream"][bad].astype(np.int64), word[bad])
+    return words.view(PROTO_VERDICT)
+
+
+def checked_reply_plan(msgs, verdict, reply_op, mask, send_keys=None, n_streams=None):
+    """The sizes and offsets of wsg_reply_checked's output (not its bytes).
+
+    ``msgs``: a message_plan table; ``verdict``: the effective PROTO_VERDICT
+    per stream (merge_verdicts); the rest as reply_plan.  A message whose FIN
+    frame lies in front of its stream's terminal frame is sized as reply_plan
+    sizes it, any other gets nothing, and the terminal frame holds the close
+    frame (status 1005 sent as 1000).  Returns (reply_off, stream_reply,
+    close_off, count): reply_off[m] the reply bytes, close frames included,
+    of the frames in front of message m's FIN frame (len(msgs) + 1 entries,
+    the last the total); n_streams + 1 stream offsets; per stream the close
+    frame's offset or 2**64 - 1; count = [reply bytes, reply frames (both with
+    the close frames), close frames]."""
+    msgs = np.asarray(msgs, dtype=MSG)
+    verdict = np.asarray(verdict, dtype=PROTO_VERDICT)
+    if n_streams is None:
+        n_streams = len(verdict)
+    sizes = np.diff(reply_plan(msgs, reply_op, mask, send_keys, n_streams=n_streams)[0].astype(np.int64))
+    fin = msgs["first_frame"].astype(np.int64) + msgs["nframes"].astype(np.int64) - 1
+    has = _verdict_words(verdict) != U64_MAX if n_streams else np.zeros(0, dtype=bool)
+    term = np.where(has, verdict["frame"].astype(np.int64), np.int64(2**62))
+    if len(msgs):
+        sizes = np.where(fin < term[msgs["stream"]], sizes, 0)
+    status = np.where(verdict["status"] == 1005, 1000, verdict["status"]).astype(np.int64)
+    closing = np.nonzero(has)[0]
+    close_size = np.array([frame_size(WS_FIN | WS_CLOSE, mask, 0, int(status[j])) for j in closing], dtype=np.int64)
+    close_frame = term[closing]
+    # bytes that belong to frames in front of frame k: replies by their FIN frame, close frames by their terminal one
+    at = np.concatenate([fin, close_frame])
+    size = np.concatenate([sizes, close_size]).astype(np.int64)
+    order = np.argsort(at, kind="stable")
+    at_sorted, cum = at[order], np.concatenate([[0], np.cumsum(size[order])])
+
+    def before(k):
+        return cum[np.searchsorted(at_sorted, k, side="left")]
+
+    total = int(cum[-1])
+    reply_off = np.concatenate([before(fin), [total]]).astype(np.uint64)
+    # stream j's first frame: its first message's first frame or its terminal frame, whichever is there;
+    # messages are stream-major and frames too, so the bytes in front of stream j are those of lower streams
+    per_stream = np.zeros(n_streams + 1, dtype=np.int64)
+    if len(msgs):
+        np.add.at(per_stream, msgs["stream"].astype(np.int64) + 1, sizes)
+    np.add.at(per_stream, closing + 1, close_size)
+    stream_reply = np.cumsum(per_stream).astype(np.uint64)
+    close_off = np.full(n_streams, U64_MAX, dtype=np.uint64)
+    close_off[closing] = before(close_frame).astype(np.uint64)
+    count = np.array([total, int((sizes > 0).sum()) + len(closing), len(closing)], dtype=np.uint64)
+    return reply_off, stream_reply, close_off, count

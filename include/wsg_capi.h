@@ -24,8 +24,9 @@
  * block, piece records) and wsg_frame_streams calls a third (per-stream frame
  * counts, scan partials; wsg_decode_streams and wsg_reply_streams are one
  * call of each of the last two) and wsg_check_protocol calls a fourth (the
- * frames' streams, scan partials, per-stream states);
- * wsg_decode_batch, wsg_check_utf8 and the fan-out calls use none.  The calls that
+ * frames' streams, scan partials, per-stream states; wsg_reply_checked uses
+ * the second and the fourth and is ordered with the users of both);
+ * wsg_decode_batch, wsg_check_utf8, wsg_utf8_verdicts and the fan-out calls use none.  The calls that
  * share a scratch are ordered across streams on the device, in the order they
  * were made: a call on another stream than the previous one first waits
  * (hipStreamWaitEvent, no host synchronisation) for an event recorded behind
@@ -34,8 +35,8 @@
  * is capturing is not ordered: it neither waits nor records, so the caller
  * keeps other users of that scratch off the device while the graph runs.  A
  * graph holding wsg_encode_batch / wsg_decode_messages / wsg_reply_messages /
- * wsg_frame_streams / wsg_check_protocol launches (wsg_decode_streams and wsg_reply_streams
- * synchronise and cannot be captured) names the
+ * wsg_frame_streams / wsg_check_protocol / wsg_reply_checked launches (the _streams
+ * forms synchronise and cannot be captured) names the
  * scratch addresses it was captured with; a later call that needs a larger
  * scratch frees them (after a device synchronise), and the graph must not be
  * replayed after that: give such a graph a ctx of its own.  Capture no call
@@ -493,6 +494,122 @@ int wsg_check_protocol(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
  * code (0 with code 0).                                                     */
 int wsg_proto_judge(const wsg_recv_info* info, const uint8_t* wire, const wsg_proto_state* before,
                     uint32_t role, uint64_t max_message, wsg_proto_state* after, uint16_t* status);
+
+/* ---- checked replies: an echo server that fails connections on the device -- */
+/* (Added without an ABI bump, as wsg_decode_messages was: symbols and
+ * constants only.)
+ *
+ * wsg_reply_messages with wsg_check_protocol run inside it, in one
+ * asynchronous call with no host round trip: replies stop at a stream's
+ * terminal frame, a close frame carrying the verdict's status is appended to
+ * that stream's range of d_reply, and the peer's own close is answered with a
+ * close.  Every payload byte is still read once and written once; the header
+ * pass and the protocol check share one d_info.
+ *
+ * What it runs.  The protocol check runs on the d_info that the plan's header
+ * pass has just written, before any reply is sized.  d_info, d_msgs, d_state,
+ * d_count[0..1], the frame-error latch and the reply_op / mask / d_send_key
+ * rules are exactly those of wsg_reply_messages; every message record is
+ * still written, answered or not.
+ * d_verdict, d_proto, d_result are as wsg_check_protocol writes them when
+ * given this call's d_state (d_proto[j] comes out as the state behind the
+ * stream's last consumed frame), d_verdict and d_result taken over the
+ * effective verdicts: with d_also == NULL the effective verdict of stream j
+ * is the protocol's; otherwise whichever of the two has the lower `frame`,
+ * and at equal frames the protocol's unless its code is WSG_PV_CLOSED and
+ * d_also[j].code >= 2 (a violation beats a clean close).  An all-0xFF entry
+ * of d_also means none.  d_also entries name frames of this call's frame
+ * table; an entry whose frame lies outside stream j's range is ignored.
+ * Terminal frame.  Let t be the `frame` of stream j's effective verdict, if
+ * it has one.  A message of stream j whose FIN frame has an index below t is
+ * answered as by wsg_reply_messages; one whose FIN frame is t or behind it
+ * gets no reply.  The stream gets one close frame:
+ * PrepareSendFrame(WSG_FIN | WSG_CLOSE, mask, NULL, 0, status) with
+ * _ws_send_mask = d_send_key[j], status the verdict's with 1005 replaced by
+ * 1000 (1005 never goes on the wire, RFC 6455 7.4.1): 4 bytes, 8 when masked
+ * (2 and 6 for a d_also entry of status 0, which has no prefix).  It is
+ * emitted even when t lies in the stream's tail and the stream has no message
+ * at all.  reply_op[WSG_CB_CLOSE] still applies to close-kind messages in
+ * front of t; the legal close frame itself is t, so it is answered by this
+ * close frame and not twice.
+ * Layout.  Every reply belongs to its message's FIN frame, every close frame
+ * to its terminal frame, and d_reply holds them in frame order, so a stream's
+ * close frame is the last thing in its range.
+ *   d_stream_reply[0..n_streams] as wsg_reply_messages; range j includes the
+ *                                close frame
+ *   d_reply_off[0..d_count[0]]   the reply bytes, close frames included, that
+ *                                belong to frames in front of message m's FIN
+ *                                frame: the start of an answered message's
+ *                                frame, whose length is the frame's own (a
+ *                                close frame may lie between it and
+ *                                d_reply_off[m+1]); [d_count[0]] is the total
+ *   d_close_off[0..n_streams)    the offset of stream j's close frame,
+ *                                UINT64_MAX when it has none
+ *   d_count[0..5)                messages, bytes of the dense layout, reply
+ *                                bytes and reply frames (both with the close
+ *                                frames), close frames
+ * Sums and counts: deterministic.  wire_len + 14 * n still suffices for
+ * reply_cap: the frames of the unanswered message that holds t (or t itself,
+ * in the tail) pay for the close frame.  When the total exceeds reply_cap no
+ * byte of d_reply is written and WSG_ENOMEM is latched behind every frame
+ * error; all tables are final either way.
+ * Arguments: checked like both calls' together (WSG_EINVAL for a NULL operand
+ * other than d_also and d_send_key, d_wire / d_reply not 16-byte aligned, any
+ * other operand not 8-byte aligned (4 for d_stream_first and d_send_key),
+ * role > 2).  n == 0, n_streams == 0 and empty streams are valid: no close
+ * frame, all-0xFF verdicts, d_close_off all UINT64_MAX.
+ * Streams: the call uses two scratches of the ctx, the message plan's and the
+ * protocol plan's, and enters and leaves both orders, so it is ordered
+ * against every other user of either (see "Streams" above); the capture rule
+ * is the usual one: run it once uncaptured with the same n and n_streams
+ * first.  The timing hook brackets the gather, as in wsg_reply_messages.     */
+#define WSG_PV_UTF8           13  /* wsg_utf8_verdicts: an invalid text message or close reason (1007) */
+
+int wsg_reply_checked(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
+                      const uint64_t* d_frame_start, uint32_t n,
+                      const uint32_t* d_stream_first, uint32_t n_streams,
+                      wsg_stream_state* d_state,
+                      wsg_proto_state* d_proto, uint32_t role, uint64_t max_message,
+                      const wsg_proto_verdict* d_also /* or NULL */,
+                      const uint8_t reply_op[5], int mask, const uint32_t* d_send_key,
+                      uint8_t* d_reply, uint64_t reply_cap,
+                      uint64_t* d_reply_off, uint64_t* d_stream_reply, uint64_t* d_close_off,
+                      wsg_proto_verdict* d_verdict, uint64_t* d_result,
+                      wsg_msg* d_msgs, uint64_t* d_count /* 5 words */,
+                      wsg_recv_info* d_info, void* stream);
+
+/* Raw bytes to checked replies: wsg_reply_streams with wsg_reply_checked in
+ * the place of wsg_reply_messages (no d_also: the frame table does not exist
+ * before the call); the same returns and the same lowering of
+ * d_span[j].consumed.  An echo server's loop is this call, one send per
+ * d_stream_reply range, and a disconnect of every stream whose d_close_off is
+ * not UINT64_MAX.                                                            */
+int wsg_reply_checked_streams(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
+                              wsg_stream_span* d_span, uint32_t n_streams, wsg_stream_state* d_state,
+                              uint64_t* d_frame_start, uint32_t frame_cap, uint32_t* d_stream_first,
+                              wsg_proto_state* d_proto, uint32_t role, uint64_t max_message,
+                              const uint8_t reply_op[5], int mask, const uint32_t* d_send_key,
+                              uint8_t* d_reply, uint64_t reply_cap,
+                              uint64_t* d_reply_off, uint64_t* d_stream_reply, uint64_t* d_close_off,
+                              wsg_proto_verdict* d_verdict, uint64_t* d_result,
+                              wsg_msg* d_msgs, uint64_t* d_count, wsg_recv_info* d_info,
+                              uint32_t* n_frames_out, void* stream);
+
+/* The result of wsg_check_utf8 as a d_also of wsg_reply_checked, behind
+ * wsg_decode_messages + wsg_check_utf8 on the same frame table: every
+ * d_also[j] is set to all 0xFF, then to the minimum, as one little-endian
+ * word, of {code WSG_PV_UTF8, status 1007, frame = first_frame + nframes - 1}
+ * over the stream's messages m < min(d_count[0], msg_room) that `which`
+ * selects (the rule of wsg_check_utf8) and whose d_valid[m] < len: the
+ * stream's first invalid message fails it at its FIN frame.  Uses no scratch,
+ * latches nothing; asynchronous on `stream`.  A validating echo server is
+ * wsg_decode_messages -> wsg_check_utf8 -> wsg_utf8_verdicts ->
+ * wsg_reply_checked(d_also), all on one stream with no synchronisation.  Its
+ * cost: the payload is moved twice, once into d_msg for the check and once
+ * into the reply (validating straight from the masked wire is not done).     */
+int wsg_utf8_verdicts(wsg_ctx* ctx, const wsg_msg* d_msgs, const uint64_t* d_count, uint32_t msg_room,
+                      uint32_t which, const uint64_t* d_valid, uint32_t n_streams,
+                      wsg_proto_verdict* d_also, void* stream);
 
 /* ---- batch encode: header pack + mask (PrepareSendFrame over many frames) */
 /* Frames are written back to back into d_wire (16-byte aligned, capacity

@@ -1,7 +1,8 @@
 """Register/occupancy report for k_decode and source variants with paths cut
 out (which path sets the kernel's VGPR count), and for k_msg_gather
 (wsg_decode_messages; wsg_reply_messages runs it too), the reply plan, the
-framer, the UTF-8 check and the protocol check.  Compiles for gfx950 only (no GPU needed).
+framer, the UTF-8 check, the protocol check and the checked reply
+(wsg_reply_checked).  Compiles for gfx950 only (no GPU needed).
 
 usage: python tools/regs.py
 """
@@ -53,11 +54,14 @@ if __name__ == "__main__":
     report(cut(src, staged), "no-staged")
     report(cut(src, boundary), "no-boundary")
     report(cut(cut(src, staged), boundary), "no-staged-no-boundary")
-    for name, kernels in (("wsg_messages.hip", ("k_msg_gather", "k_msg_finalize", "k_reply_local", "k_reply_blocks",
-                                                "k_reply_finalize")),
+    for name, kernels in (("wsg_messages.hip", ("k_msg_gather", "k_msg_finalize", "k_reply_local<0>", "k_reply_blocks<0>",
+                                                "k_reply_finalize<0>", "k_msg_consumed", "k_reply_local<1>",
+                                                "k_reply_blocks<1>", "k_reply_finalize<1>")),
                           ("wsg_frames.hip", ("k_frame_count", "k_frame_write")),
-                          ("wsg_utf8.hip", ("k_utf8_init", "k_utf8_scan", "k_utf8_count")),
-                          ("wsg_proto.hip", ("k_proto_local", "k_proto_blocks", "k_proto_judge", "k_proto_finish"))):
+                          ("wsg_utf8.hip", ("k_utf8_init", "k_utf8_scan", "k_utf8_count", "k_utf8_verdict_seed", "k_utf8_verdicts")),
+                          ("wsg_proto.hip", ("k_proto_local", "k_proto_blocks", "k_proto_judge", "k_proto_finish",
+                                             "k_proto_merge"))):
         src = source(name)
         for k in kernels:
-            report(src, k, kernel="_ZN3wsg%d%s" % (len(k), k))
+            base, _, flag = k.partition("<")   # name<0|1>: an instantiation of a template on one bool
+            report(src, k, kernel="_ZN3wsg%d%s" % (len(base), base) + ("ILb%sEE" % flag[0] if flag else ""))
