@@ -1,0 +1,680 @@
+// wsg_capi_device.cpp — the device-resident entry points of include/wsg_capi.h
+// (wsg_decode_batch through wsg_fanout_encode_many): argument checks, scratch,
+// launches.  Operands are device memory; nothing here synchronises but
+// wsg_*_streams, which read a frame count back.
+#include "wsg_ctx.h"
+
+#include <vector>
+
+int decode_launch(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const uint64_t* d_frame_start, uint32_t n,
+                  uint8_t* d_out, wsg_recv_info* d_info, hipStream_t s, unsigned long long* err)
+{
+    if (n == 0) {
+        if (wire_len && d_out != d_wire)
+            WSG_HIP(hipMemcpyAsync(d_out, d_wire, wire_len, hipMemcpyDeviceToDevice, s));
+        return WSG_OK;
+    }
+    // every tile, and at least one block per 256 frames so that the frames of
+    // a short (or empty) wire are still checked
+    const uint64_t tiles = ceil_div(wire_len, wsg::TILE);
+    const int t = timing_begin(c, s);
+    WSG_HIP(wsg::launch_decode(s, grid_for(c, std::max(tiles, ceil_div(n, wsg::BLOCK)), c->dec_blocks_per_cu), d_wire, d_out, wire_len,
+                               d_frame_start, n, d_info, err));
+    timing_end(c, s, t);
+    return WSG_OK;
+}
+
+namespace {
+
+// upper bound of the pieces: sum of ceil((size + 15) / PIECE) over frames
+inline uint64_t pieces_bound(uint32_t n, uint64_t wire_cap) { return wire_cap / wsg::PIECE + 2 * uint64_t(n) + 1; }
+
+// The scratch of wsg_decode_messages / wsg_reply_messages for n frames of a
+// wire of wire_len bytes: the plan block and the piece records.  Pieces: at
+// most len / PIECE + 2 per delivered frame, and the delivered payloads of a
+// well-formed batch are disjoint ranges of the wire (the kernels clamp to
+// this bound whatever the batch holds); a reply cuts the same frames at
+// 16-byte chunks of another destination.  Both are the context's: entered
+// behind the previous call's kernels, whatever stream they ran on.
+int msg_scratch(wsg_ctx* c, hipStream_t s, uint32_t n, uint64_t wire_len, wsg::MsgPlan* plan, uint64_t* pieces_cap,
+                bool* ordered)
+{
+    *pieces_cap = pieces_bound(n, wire_len);
+    if (*pieces_cap > UINT32_MAX)
+        return WSG_EINVAL;
+    if (int rc = ensure_array(c->d_msg_plan, c->msg_plan_cap, wsg::msg_plan_layout(nullptr, n, nullptr)))
+        return rc;
+    if (int rc = ensure_array(c->d_msg_pieces, c->msg_pieces_cap, *pieces_cap))
+        return rc;
+    wsg::msg_plan_layout(c->d_msg_plan, n, plan);
+    return scratch_enter(c->msg_order, s, ordered);
+}
+
+// The scratch of wsg_check_protocol / wsg_reply_checked for n frames in
+// n_streams streams: the plan block, the context's, entered as msg_scratch's.
+int proto_scratch(wsg_ctx* c, hipStream_t s, uint32_t n, uint32_t n_streams, wsg::ProtoPlan* plan, bool* ordered)
+{
+    if (int rc = ensure_array(c->d_proto_plan, c->proto_plan_cap, wsg::proto_plan_layout(nullptr, n, n_streams, nullptr)))
+        return rc;
+    wsg::proto_plan_layout(c->d_proto_plan, n, n_streams, plan);
+    return scratch_enter(c->proto_order, s, ordered);
+}
+
+wsg::ReplyRule make_rule(const uint8_t reply_op[5], int mask)
+{
+    wsg::ReplyRule rule;
+    for (int k = 0; k < 5; ++k)
+        rule.op[k] = reply_op[k];
+    rule.mask = mask ? 1 : 0;
+    return rule;
+}
+
+// The gather over the plan's piece records, the timed kernel of its call:
+// `launch` is launch_msg_gather (every delivered payload byte to d_msg) or
+// launch_reply_gather (re-keyed, to the reply wire).
+int gather_launch(wsg_ctx* c, hipStream_t s, decltype(wsg::launch_msg_gather)* launch, const uint8_t* d_wire,
+                  const wsg::MsgPlan& plan, uint64_t pieces_cap, uint8_t* d_dst, uint64_t dst_cap)
+{
+    const int t = timing_begin(c, s);
+    WSG_HIP(launch(s, grid_for(c, ceil_div(pieces_cap, wsg::BLOCK / 64), c->enc_blocks_per_cu), d_wire, plan,
+                   c->d_msg_pieces, pieces_cap, d_dst, dst_cap));
+    timing_end(c, s, t);
+    return WSG_OK;
+}
+
+} // namespace
+
+int wsg_decode_batch(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const uint64_t* d_frame_start, uint32_t n,
+                     uint8_t* d_out, wsg_recv_info* d_info, void* stream)
+{
+    if (!c || (wire_len && (!d_wire || !d_out)) || (n && (!d_frame_start || !d_info)))
+        return WSG_EINVAL;
+    if (!aligned16(d_wire) || !aligned16(d_out))
+        return WSG_EINVAL;
+    if (c->check && (!in_alloc(d_wire, (wire_len + 15) & ~uint64_t(15)) || !in_alloc(d_out, wire_len) ||
+                     !in_alloc(d_frame_start, uint64_t(n) * 8) || !in_alloc(d_info, uint64_t(n) * sizeof(wsg_recv_info))))
+        return WSG_EINVAL;
+    return decode_launch(c, d_wire, wire_len, d_frame_start, n, d_out, d_info, as_stream(stream), c->d_err);
+}
+
+// Messages out of a batch of frames: the plan pass (a few small kernels, one
+// lane per frame or per stream), then the gather, which moves every
+// delivered payload byte once.
+int wsg_decode_messages(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const uint64_t* d_frame_start,
+                        uint32_t n, const uint32_t* d_stream_first, uint32_t n_streams, wsg_stream_state* d_state,
+                        uint8_t* d_msg, uint64_t msg_cap, wsg_msg* d_msgs, uint64_t* d_count, wsg_recv_info* d_info,
+                        void* stream)
+{
+    if (!c || !d_count || !d_stream_first || (wire_len && !d_wire) || (msg_cap && !d_msg) ||
+        (n && (!d_frame_start || !d_info || !d_msgs || n_streams == 0)) || (n_streams && !d_state) ||
+        n == UINT32_MAX || n_streams == UINT32_MAX)
+        return WSG_EINVAL;
+    if (!aligned16(d_wire) || !aligned16(d_msg))
+        return WSG_EINVAL;
+    if (c->check &&
+        (!in_alloc(d_wire, (wire_len + 15) & ~uint64_t(15)) || !in_alloc(d_frame_start, uint64_t(n) * 8) ||
+         !in_alloc(d_stream_first, (uint64_t(n_streams) + 1) * 4) ||
+         !in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) || !in_alloc(d_msg, msg_cap) ||
+         !in_alloc(d_msgs, uint64_t(n) * sizeof(wsg_msg)) || !in_alloc(d_count, 2 * 8) ||
+         !in_alloc(d_info, uint64_t(n) * sizeof(wsg_recv_info))))
+        return WSG_EINVAL;
+    hipStream_t s = as_stream(stream);
+    wsg::MsgPlan plan;
+    uint64_t pieces_cap;
+    bool ordered = false;
+    if (int rc = msg_scratch(c, s, n, wire_len, &plan, &pieces_cap, &ordered))
+        return rc;
+    WSG_HIP(wsg::launch_msg_plan(s, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams, d_state, msg_cap,
+                                 d_msgs, d_count, d_info, plan, c->d_msg_pieces, pieces_cap, c->d_err));
+    if (n)
+        if (int rc = gather_launch(c, s, wsg::launch_msg_gather, d_wire, plan, pieces_cap, d_msg, msg_cap))
+            return rc;
+    return scratch_leave(c->msg_order, s, ordered);
+}
+
+// UTF-8 over the messages of a decode: one lane per record before and behind
+// the payload kernel, which reads every byte of d_msg below the bound once.
+int wsg_check_utf8(wsg_ctx* c, const uint8_t* d_msg, uint64_t msg_cap, const wsg_msg* d_msgs, const uint64_t* d_count,
+                   uint32_t msg_room, uint32_t which, uint64_t* d_valid, uint64_t* d_result, void* stream)
+{
+    if (!c || !d_count || !d_result || (msg_cap && !d_msg) || (msg_room && (!d_msgs || !d_valid)))
+        return WSG_EINVAL;
+    if (!aligned16(d_msg) || !aligned8(d_msgs) || !aligned8(d_count) || !aligned8(d_valid) || !aligned8(d_result))
+        return WSG_EINVAL;
+    if (c->check && (!in_alloc(d_msg, msg_cap) || !in_alloc(d_msgs, uint64_t(msg_room) * sizeof(wsg_msg)) ||
+                     !in_alloc(d_valid, uint64_t(msg_room) * 8) || !in_alloc(d_count, 2 * 8) ||
+                     !in_alloc(d_result, 4 * 8)))
+        return WSG_EINVAL;
+    hipStream_t s = as_stream(stream);
+    const int rec_grid = grid_for(c, ceil_div(msg_room, wsg::BLOCK));   // (at least one block: it seeds d_result)
+    WSG_HIP(wsg::launch_utf8_init(s, rec_grid, d_msgs, d_count, msg_room, d_valid, d_result));
+    if (msg_room == 0)
+        return WSG_OK;
+    if (which && msg_cap) {
+        const int t = timing_begin(c, s);
+        WSG_HIP(wsg::launch_utf8_scan(s, grid_for(c, ceil_div(msg_cap, uint64_t(wsg::BLOCK) * wsg::CHUNK), c->utf8_blocks_per_cu),
+                                      d_msg, msg_cap, d_msgs, d_count, msg_room, which, d_valid));
+        timing_end(c, s, t);
+    }
+    WSG_HIP(wsg::launch_utf8_count(s, rec_grid, d_msgs, d_count, msg_room, msg_cap, which, d_valid, d_result));
+    return WSG_OK;
+}
+
+// The frame-sequence rules over a decoded batch: a scan of the frames' steps
+// on their stream's state, the judging kernel (one lane per frame), one lane
+// per stream behind it.
+int wsg_check_protocol(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const wsg_recv_info* d_info, uint32_t n,
+                       const uint32_t* d_stream_first, uint32_t n_streams, const wsg_stream_state* d_state,
+                       wsg_proto_state* d_proto, uint32_t role, uint64_t max_message, wsg_proto_verdict* d_verdict,
+                       uint64_t* d_result, void* stream)
+{
+    if (!c || !d_info || !d_stream_first || !d_proto || !d_verdict || !d_result || (wire_len && !d_wire) ||
+        role > WSG_PROTO_CLIENT || n == UINT32_MAX || n_streams == UINT32_MAX)
+        return WSG_EINVAL;
+    if (!aligned8(d_info) || (reinterpret_cast<uintptr_t>(d_stream_first) & 3u) || !aligned8(d_state) ||
+        !aligned8(d_proto) || !aligned8(d_verdict) || !aligned8(d_result))
+        return WSG_EINVAL;
+    if (c->check && (!in_alloc(d_wire, wire_len) || !in_alloc(d_info, uint64_t(n) * sizeof(wsg_recv_info)) ||
+                     !in_alloc(d_stream_first, (uint64_t(n_streams) + 1) * 4) ||
+                     (d_state && !in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state))) ||
+                     !in_alloc(d_proto, uint64_t(n_streams) * sizeof(wsg_proto_state)) ||
+                     !in_alloc(d_verdict, uint64_t(n_streams) * sizeof(wsg_proto_verdict)) || !in_alloc(d_result, 3 * 8)))
+        return WSG_EINVAL;
+    hipStream_t s = as_stream(stream);
+    wsg::ProtoPlan plan;
+    bool ordered = false;
+    if (int rc = proto_scratch(c, s, n, n_streams, &plan, &ordered))
+        return rc;
+    WSG_HIP(wsg::launch_proto_scan(s, d_info, n, d_stream_first, n_streams, d_proto, plan, d_verdict, d_result));
+    if (n && n_streams) {
+        const int t = timing_begin(c, s);
+        WSG_HIP(wsg::launch_proto_judge(s, d_wire, wire_len, d_info, n, d_stream_first, d_state, d_proto, role,
+                                        max_message, plan, d_verdict));
+        timing_end(c, s, t);
+    }
+    WSG_HIP(wsg::launch_proto_finish(s, grid_for(c, ceil_div(n_streams, wsg::BLOCK)), n, d_stream_first, n_streams,
+                                     d_state, d_proto, plan, d_verdict, d_result));
+    return scratch_leave(c->proto_order, s, ordered);
+}
+
+// The device framer: two walks over every stream (one wave each) with a scan
+// of the per-stream frame counts between them.
+int wsg_frame_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_stream_span* d_span,
+                      uint32_t n_streams, uint64_t* d_frame_start, uint32_t frame_cap, uint32_t* d_stream_first,
+                      uint64_t* d_count, void* stream)
+{
+    if (!c || !d_count || !d_stream_first || (wire_len && !d_wire) || (n_streams && !d_span) ||
+        (frame_cap && !d_frame_start) || n_streams == UINT32_MAX)
+        return WSG_EINVAL;
+    if (!aligned16(d_wire))
+        return WSG_EINVAL;
+    if (c->check &&
+        (!in_alloc(d_wire, (wire_len + 15) & ~uint64_t(15)) ||
+         !in_alloc(d_span, uint64_t(n_streams) * sizeof(wsg_stream_span)) ||
+         !in_alloc(d_frame_start, uint64_t(frame_cap) * 8) ||
+         !in_alloc(d_stream_first, (uint64_t(n_streams) + 1) * 4) || !in_alloc(d_count, 2 * 8)))
+        return WSG_EINVAL;
+    hipStream_t s = as_stream(stream);
+    if (int rc = ensure_array(c->d_frame_plan, c->frame_plan_cap, wsg::frame_plan_layout(nullptr, n_streams, nullptr)))
+        return rc;
+    wsg::FramePlan plan;
+    wsg::frame_plan_layout(c->d_frame_plan, n_streams, &plan);
+    // the counts and partials are the context's: behind the previous call's
+    // kernels, whatever stream they ran on
+    bool ordered = false;
+    if (int rc = scratch_enter(c->frame_order, s, &ordered))
+        return rc;
+    const int t = n_streams ? timing_begin(c, s) : -1;
+    WSG_HIP(wsg::launch_frame_streams(s, grid_for(c, ceil_div(n_streams, wsg::BLOCK / 64), c->dec_blocks_per_cu), d_wire,
+                                      wire_len, d_span, n_streams, d_frame_start, frame_cap, d_stream_first, d_count,
+                                      plan, c->d_err));
+    timing_end(c, s, t);
+    return scratch_leave(c->frame_order, s, ordered);
+}
+
+namespace {
+
+// wsg_decode_streams and wsg_reply_streams: the framer, one synchronisation
+// to read the frame count, `messages(n)` over the frames it found, the spans'
+// consumed lowered to the first tail frame.
+template <class Messages>
+int streams_then(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_stream_span* d_span, uint32_t n_streams,
+                 wsg_stream_state* d_state, uint64_t* d_frame_start, uint32_t frame_cap, uint32_t* d_stream_first,
+                 uint64_t* d_count, uint32_t* n_frames_out, void* stream, Messages messages)
+{
+    hipStream_t s = as_stream(stream);
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    WSG_HIP(hipStreamIsCapturing(s, &cap));
+    if (cap != hipStreamCaptureStatusNone)
+        return WSG_EINVAL;   // the frame count is read on the host in the middle
+    *n_frames_out = 0;
+    if (int rc = wsg_frame_streams(c, d_wire, wire_len, d_span, n_streams, d_frame_start, frame_cap, d_stream_first,
+                                   d_count, stream))
+        return rc;
+    uint64_t found = 0;
+    WSG_HIP(hipMemcpyAsync(&found, d_count, sizeof(found), hipMemcpyDeviceToHost, s));
+    WSG_HIP(hipStreamSynchronize(s));
+    if (found > uint64_t(UINT32_MAX) - 1)
+        return WSG_EINVAL;
+    if (found > frame_cap)
+        return WSG_ENOMEM;
+    const uint32_t n = uint32_t(found);
+    *n_frames_out = n;
+    if (int rc = messages(n))
+        return rc;
+    WSG_HIP(wsg::launch_frame_tail(s, d_span, n_streams, d_frame_start, d_stream_first, d_state, n));
+    return WSG_OK;
+}
+
+} // namespace
+
+int wsg_decode_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_stream_span* d_span,
+                       uint32_t n_streams, wsg_stream_state* d_state, uint64_t* d_frame_start, uint32_t frame_cap,
+                       uint32_t* d_stream_first, uint8_t* d_msg, uint64_t msg_cap, wsg_msg* d_msgs, uint64_t* d_count,
+                       wsg_recv_info* d_info, uint32_t* n_frames_out, void* stream)
+{
+    if (!c || !n_frames_out || !d_count || (n_streams && !d_state) || (msg_cap && !d_msg) ||
+        (frame_cap && (!d_msgs || !d_info)) || !aligned16(d_msg))
+        return WSG_EINVAL;
+    if (c->check && (!in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) || !in_alloc(d_msg, msg_cap) ||
+                     !in_alloc(d_msgs, uint64_t(frame_cap) * sizeof(wsg_msg)) ||
+                     !in_alloc(d_info, uint64_t(frame_cap) * sizeof(wsg_recv_info))))
+        return WSG_EINVAL;
+    return streams_then(c, d_wire, wire_len, d_span, n_streams, d_state, d_frame_start, frame_cap, d_stream_first,
+                        d_count, n_frames_out, stream, [&](uint32_t n) {
+                            return wsg_decode_messages(c, d_wire, wire_len, d_frame_start, n, d_stream_first,
+                                                       n_streams, d_state, d_msg, msg_cap, d_msgs, d_count, d_info,
+                                                       stream);
+                        });
+}
+
+// Replies out of a batch of frames: wsg_decode_messages' plan with the reply
+// frames' geometry scanned behind it, then the same gather, its destination
+// the reply wire.
+int wsg_reply_messages(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const uint64_t* d_frame_start, uint32_t n,
+                       const uint32_t* d_stream_first, uint32_t n_streams, wsg_stream_state* d_state,
+                       const uint8_t reply_op[5], int mask, const uint32_t* d_send_key, uint8_t* d_reply,
+                       uint64_t reply_cap, uint64_t* d_reply_off, uint64_t* d_stream_reply, wsg_msg* d_msgs,
+                       uint64_t* d_count, wsg_recv_info* d_info, void* stream)
+{
+    if (!c || !d_count || !d_stream_first || !reply_op || !d_reply_off || !d_stream_reply || (wire_len && !d_wire) ||
+        (reply_cap && !d_reply) || (n && (!d_frame_start || !d_info || !d_msgs || n_streams == 0)) ||
+        (n_streams && !d_state) || n == UINT32_MAX || n_streams == UINT32_MAX)
+        return WSG_EINVAL;
+    if (!aligned16(d_wire) || !aligned16(d_reply))
+        return WSG_EINVAL;
+    if (c->check &&
+        (!in_alloc(d_wire, (wire_len + 15) & ~uint64_t(15)) || !in_alloc(d_frame_start, uint64_t(n) * 8) ||
+         !in_alloc(d_stream_first, (uint64_t(n_streams) + 1) * 4) ||
+         !in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) ||
+         (d_send_key && !in_alloc(d_send_key, uint64_t(n_streams) * 4)) || !in_alloc(d_reply, reply_cap) ||
+         !in_alloc(d_reply_off, (uint64_t(n) + 1) * 8) || !in_alloc(d_stream_reply, (uint64_t(n_streams) + 1) * 8) ||
+         !in_alloc(d_msgs, uint64_t(n) * sizeof(wsg_msg)) || !in_alloc(d_count, 4 * 8) ||
+         !in_alloc(d_info, uint64_t(n) * sizeof(wsg_recv_info))))
+        return WSG_EINVAL;
+    hipStream_t s = as_stream(stream);
+    wsg::MsgPlan plan;
+    uint64_t pieces_cap;
+    bool ordered = false;
+    if (int rc = msg_scratch(c, s, n, wire_len, &plan, &pieces_cap, &ordered))
+        return rc;
+    WSG_HIP(wsg::launch_reply_plan(s, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams, d_state,
+                                   make_rule(reply_op, mask), d_send_key, d_reply, reply_cap, d_reply_off,
+                                   d_stream_reply, d_msgs, d_count, d_info, plan, c->d_msg_pieces, pieces_cap,
+                                   c->d_err));
+    if (n)
+        if (int rc = gather_launch(c, s, wsg::launch_reply_gather, d_wire, plan, pieces_cap, d_reply, reply_cap))
+            return rc;
+    return scratch_leave(c->msg_order, s, ordered);
+}
+
+int wsg_reply_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_stream_span* d_span,
+                      uint32_t n_streams, wsg_stream_state* d_state, uint64_t* d_frame_start, uint32_t frame_cap,
+                      uint32_t* d_stream_first, const uint8_t reply_op[5], int mask, const uint32_t* d_send_key,
+                      uint8_t* d_reply, uint64_t reply_cap, uint64_t* d_reply_off, uint64_t* d_stream_reply,
+                      wsg_msg* d_msgs, uint64_t* d_count, wsg_recv_info* d_info, uint32_t* n_frames_out, void* stream)
+{
+    if (!c || !n_frames_out || !d_count || !reply_op || !d_reply_off || !d_stream_reply || (n_streams && !d_state) ||
+        (reply_cap && !d_reply) || (frame_cap && (!d_msgs || !d_info)) || !aligned16(d_reply))
+        return WSG_EINVAL;
+    if (c->check &&
+        (!in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) || !in_alloc(d_reply, reply_cap) ||
+         !in_alloc(d_reply_off, (uint64_t(frame_cap) + 1) * 8) ||
+         !in_alloc(d_msgs, uint64_t(frame_cap) * sizeof(wsg_msg)) ||
+         !in_alloc(d_info, uint64_t(frame_cap) * sizeof(wsg_recv_info))))
+        return WSG_EINVAL;
+    return streams_then(c, d_wire, wire_len, d_span, n_streams, d_state, d_frame_start, frame_cap, d_stream_first,
+                        d_count, n_frames_out, stream, [&](uint32_t n) {
+                            return wsg_reply_messages(c, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams,
+                                                      d_state, reply_op, mask, d_send_key, d_reply, reply_cap,
+                                                      d_reply_off, d_stream_reply, d_msgs, d_count, d_info, stream);
+                        });
+}
+
+// wsg_reply_messages with wsg_check_protocol inside it: the protocol kernels
+// run on the d_info the plan's header pass has just written, and the reply
+// kernels stop every stream at its terminal frame and close it there.
+int wsg_reply_checked(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const uint64_t* d_frame_start, uint32_t n,
+                      const uint32_t* d_stream_first, uint32_t n_streams, wsg_stream_state* d_state,
+                      wsg_proto_state* d_proto, uint32_t role, uint64_t max_message, const wsg_proto_verdict* d_also,
+                      const uint8_t reply_op[5], int mask, const uint32_t* d_send_key, uint8_t* d_reply,
+                      uint64_t reply_cap, uint64_t* d_reply_off, uint64_t* d_stream_reply, uint64_t* d_close_off,
+                      wsg_proto_verdict* d_verdict, uint64_t* d_result, wsg_msg* d_msgs, uint64_t* d_count,
+                      wsg_recv_info* d_info, void* stream)
+{
+    if (!c || !d_count || !d_stream_first || !reply_op || !d_reply_off || !d_stream_reply || !d_close_off ||
+        !d_proto || !d_verdict || !d_result || (wire_len && !d_wire) || (reply_cap && !d_reply) ||
+        (n && (!d_frame_start || !d_info || !d_msgs || n_streams == 0)) || (n_streams && !d_state) ||
+        role > WSG_PROTO_CLIENT || n == UINT32_MAX || n_streams == UINT32_MAX)
+        return WSG_EINVAL;
+    if (!aligned16(d_wire) || !aligned16(d_reply))
+        return WSG_EINVAL;
+    if (!aligned8(d_frame_start) || (reinterpret_cast<uintptr_t>(d_stream_first) & 3u) || !aligned8(d_state) ||
+        !aligned8(d_proto) || !aligned8(d_also) || (reinterpret_cast<uintptr_t>(d_send_key) & 3u) ||
+        !aligned8(d_reply_off) || !aligned8(d_stream_reply) || !aligned8(d_close_off) || !aligned8(d_verdict) ||
+        !aligned8(d_result) || !aligned8(d_msgs) || !aligned8(d_count) || !aligned8(d_info))
+        return WSG_EINVAL;
+    if (c->check &&
+        (!in_alloc(d_wire, (wire_len + 15) & ~uint64_t(15)) || !in_alloc(d_frame_start, uint64_t(n) * 8) ||
+         !in_alloc(d_stream_first, (uint64_t(n_streams) + 1) * 4) ||
+         !in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) ||
+         !in_alloc(d_proto, uint64_t(n_streams) * sizeof(wsg_proto_state)) ||
+         (d_also && !in_alloc(d_also, uint64_t(n_streams) * sizeof(wsg_proto_verdict))) ||
+         (d_send_key && !in_alloc(d_send_key, uint64_t(n_streams) * 4)) || !in_alloc(d_reply, reply_cap) ||
+         !in_alloc(d_reply_off, (uint64_t(n) + 1) * 8) || !in_alloc(d_stream_reply, (uint64_t(n_streams) + 1) * 8) ||
+         !in_alloc(d_close_off, uint64_t(n_streams) * 8) ||
+         !in_alloc(d_verdict, uint64_t(n_streams) * sizeof(wsg_proto_verdict)) || !in_alloc(d_result, 3 * 8) ||
+         !in_alloc(d_msgs, uint64_t(n) * sizeof(wsg_msg)) || !in_alloc(d_count, 5 * 8) ||
+         !in_alloc(d_info, uint64_t(n) * sizeof(wsg_recv_info))))
+        return WSG_EINVAL;
+    hipStream_t s = as_stream(stream);
+    // both scratches are the context's: behind the last user of either,
+    // whatever stream it ran on
+    wsg::ProtoPlan pplan;
+    wsg::MsgPlan plan;
+    uint64_t pieces_cap;
+    bool ordered = false, pordered = false;
+    if (int rc = proto_scratch(c, s, n, n_streams, &pplan, &pordered))
+        return rc;
+    if (int rc = msg_scratch(c, s, n, wire_len, &plan, &pieces_cap, &ordered))
+        return rc;
+    WSG_HIP(wsg::launch_reply_checked_plan(s, grid_for(c, ceil_div(n_streams, wsg::BLOCK)), d_wire, wire_len,
+                                           d_frame_start, n, d_stream_first, n_streams, d_state, d_proto, role,
+                                           max_message, d_also, make_rule(reply_op, mask), d_send_key, d_reply,
+                                           reply_cap, d_reply_off, d_stream_reply, d_close_off, d_verdict, d_result,
+                                           d_msgs, d_count, d_info, plan, pplan, c->d_msg_pieces, pieces_cap,
+                                           c->d_err));
+    if (n)
+        if (int rc = gather_launch(c, s, wsg::launch_reply_gather, d_wire, plan, pieces_cap, d_reply, reply_cap))
+            return rc;
+    if (int rc = scratch_leave(c->proto_order, s, pordered))
+        return rc;
+    return scratch_leave(c->msg_order, s, ordered);
+}
+
+int wsg_reply_checked_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_stream_span* d_span,
+                              uint32_t n_streams, wsg_stream_state* d_state, uint64_t* d_frame_start,
+                              uint32_t frame_cap, uint32_t* d_stream_first, wsg_proto_state* d_proto, uint32_t role,
+                              uint64_t max_message, const uint8_t reply_op[5], int mask, const uint32_t* d_send_key,
+                              uint8_t* d_reply, uint64_t reply_cap, uint64_t* d_reply_off, uint64_t* d_stream_reply,
+                              uint64_t* d_close_off, wsg_proto_verdict* d_verdict, uint64_t* d_result, wsg_msg* d_msgs,
+                              uint64_t* d_count, wsg_recv_info* d_info, uint32_t* n_frames_out, void* stream)
+{
+    if (!c || !n_frames_out || !d_count || !reply_op || !d_reply_off || !d_stream_reply || !d_close_off || !d_proto ||
+        !d_verdict || !d_result || (n_streams && !d_state) || (reply_cap && !d_reply) ||
+        (frame_cap && (!d_msgs || !d_info)) || !aligned16(d_reply) || role > WSG_PROTO_CLIENT)
+        return WSG_EINVAL;
+    if (c->check &&
+        (!in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) || !in_alloc(d_reply, reply_cap) ||
+         !in_alloc(d_reply_off, (uint64_t(frame_cap) + 1) * 8) ||
+         !in_alloc(d_msgs, uint64_t(frame_cap) * sizeof(wsg_msg)) ||
+         !in_alloc(d_info, uint64_t(frame_cap) * sizeof(wsg_recv_info))))
+        return WSG_EINVAL;
+    return streams_then(c, d_wire, wire_len, d_span, n_streams, d_state, d_frame_start, frame_cap, d_stream_first,
+                        d_count, n_frames_out, stream, [&](uint32_t n) {
+                            return wsg_reply_checked(c, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams,
+                                                     d_state, d_proto, role, max_message, nullptr, reply_op, mask,
+                                                     d_send_key, d_reply, reply_cap, d_reply_off, d_stream_reply,
+                                                     d_close_off, d_verdict, d_result, d_msgs, d_count, d_info,
+                                                     stream);
+                        });
+}
+
+// wsg_check_utf8's d_valid as the d_also of wsg_reply_checked: a seed per
+// stream, then one lane per record.
+int wsg_utf8_verdicts(wsg_ctx* c, const wsg_msg* d_msgs, const uint64_t* d_count, uint32_t msg_room, uint32_t which,
+                      const uint64_t* d_valid, uint32_t n_streams, wsg_proto_verdict* d_also, void* stream)
+{
+    if (!c || !d_count || (msg_room && (!d_msgs || !d_valid)) || (n_streams && !d_also) || n_streams == UINT32_MAX)
+        return WSG_EINVAL;
+    if (!aligned8(d_msgs) || !aligned8(d_count) || !aligned8(d_valid) || !aligned8(d_also))
+        return WSG_EINVAL;
+    if (c->check && (!in_alloc(d_msgs, uint64_t(msg_room) * sizeof(wsg_msg)) ||
+                     !in_alloc(d_valid, uint64_t(msg_room) * 8) || !in_alloc(d_count, 2 * 8) ||
+                     !in_alloc(d_also, uint64_t(n_streams) * sizeof(wsg_proto_verdict))))
+        return WSG_EINVAL;
+    if (n_streams == 0)
+        return WSG_OK;
+    WSG_HIP(wsg::launch_utf8_verdicts(as_stream(stream), grid_for(c, ceil_div(msg_room, wsg::BLOCK)),
+                                      grid_for(c, ceil_div(n_streams, wsg::BLOCK)), d_msgs, d_count, msg_room, which,
+                                      d_valid, n_streams, d_also));
+    return WSG_OK;
+}
+
+namespace {
+
+// Small-frame batches (average frame <= small_avg) take k_encode_small,
+// the rest the piece kernel.
+bool small_path(const wsg_ctx* c, uint32_t n, uint64_t wire_cap) { return wire_cap <= uint64_t(n) * c->small_avg; }
+
+} // namespace
+
+int ensure_enc(const wsg_ctx* c, wsg_enc_scratch& e, uint32_t n, uint64_t wire_cap)
+{
+    if (int rc = ensure_array(e.d_scan, e.scan_cap, 4 * ceil_div(n, wsg::SCAN_ITEMS)))
+        return rc;
+    if (int rc = ensure_array(e.d_piece_start, e.piece_start_cap, uint64_t(n) + 1))
+        return rc;
+    if (c && small_path(c, n, wire_cap))
+        return WSG_OK;
+    // pieces are indexed by u32 in the launch (q_begin / q_end): a bound past
+    // that (a wire_cap of terabytes, far past any HBM) is refused, not wrapped
+    if (pieces_bound(n, wire_cap) > UINT32_MAX)
+        return WSG_EINVAL;
+    return ensure_array(e.d_piece_frame, e.piece_frame_cap, pieces_bound(n, wire_cap));
+}
+
+int encode_launch(wsg_ctx* c, hipStream_t s, const uint8_t* d_payload, const wsg_send_desc* d_desc, uint32_t n,
+                  uint8_t* d_wire, uint64_t wire_cap, uint64_t* d_wire_off, wsg_enc_scratch& e,
+                  unsigned long long* err)
+{
+    if (small_path(c, n, wire_cap)) {   // sizes scan, then one block per group of frames
+        WSG_HIP(wsg::launch_encode_scan_small(s, d_desc, n, d_wire_off, e.d_scan));
+        const int t = timing_begin(c, s);
+        WSG_HIP(wsg::launch_encode_small(s, d_payload, d_desc, n, d_wire_off, e.d_scan, d_wire, wire_cap, err));
+        timing_end(c, s, t);
+        return WSG_OK;
+    }
+    const uint64_t pieces_cap = pieces_bound(n, wire_cap);
+    if (pieces_cap > UINT32_MAX)   // as ensure_enc: u32 piece indices below
+        return WSG_EINVAL;
+    WSG_HIP(wsg::launch_encode_scan(s, d_desc, n, d_wire_off, e.d_piece_start, e.d_scan, e.d_piece_frame, pieces_cap,
+                                    wire_cap, err));
+    // one launch per run of at most enc_launch_pieces pieces (0: one launch)
+    const uint64_t per = c->enc_launch_pieces ? c->enc_launch_pieces : pieces_cap;
+    const int t = timing_begin(c, s);
+    for (uint64_t q0 = 0; q0 < pieces_cap; q0 += per) {
+        const uint64_t q1 = std::min<uint64_t>(pieces_cap, q0 + per);
+        WSG_HIP(wsg::launch_encode_mask(s, grid_for(c, ceil_div(q1 - q0, wsg::BLOCK / 64), c->enc_blocks_per_cu),
+                                        d_payload, d_desc, n, d_wire_off, e.d_piece_start, e.d_piece_frame, d_wire,
+                                        wire_cap, uint32_t(q0), uint32_t(q1)));
+    }
+    timing_end(c, s, t);
+    return WSG_OK;
+}
+
+int wsg_encode_batch(wsg_ctx* c, const uint8_t* d_payload, const wsg_send_desc* d_desc, uint32_t n, uint8_t* d_wire,
+                     uint64_t wire_cap, uint64_t* d_wire_off, void* stream)
+{
+    if (!c || !d_wire_off || (n && (!d_desc || !d_wire)))
+        return WSG_EINVAL;
+    if (!aligned16(d_wire))
+        return WSG_EINVAL;
+    hipStream_t s = as_stream(stream);
+    if (n == 0) {
+        WSG_HIP(hipMemsetAsync(d_wire_off, 0, sizeof(uint64_t), s));
+        return WSG_OK;
+    }
+    if (c->check) {   // the descriptors come to the host: every payload range and the wire capacity
+        if (!in_alloc(d_desc, uint64_t(n) * sizeof(wsg_send_desc)) || !in_alloc(d_wire, wire_cap) ||
+            !in_alloc(d_wire_off, (uint64_t(n) + 1) * 8))
+            return WSG_EINVAL;
+        std::vector<wsg_send_desc> h;
+        try {
+            h.resize(n);
+        } catch (...) {
+            return WSG_ENOMEM;
+        }
+        WSG_HIP(hipMemcpyAsync(h.data(), d_desc, uint64_t(n) * sizeof(wsg_send_desc), hipMemcpyDeviceToHost, s));
+        WSG_HIP(hipStreamSynchronize(s));
+        for (const wsg_send_desc& d : h)
+            if (d.len && (!d_payload || !in_alloc(d_payload + d.src_off, d.len)))
+                return WSG_EINVAL;
+    }
+    if (int rc = ensure_enc(c, c->enc, n, wire_cap))
+        return rc;
+    // c->enc is the context's: behind the previous call's kernels, whatever
+    // stream they ran on
+    bool ordered = false;
+    if (int rc = scratch_enter(c->enc_order, s, &ordered))
+        return rc;
+    if (int rc = encode_launch(c, s, d_payload, d_desc, n, d_wire, wire_cap, d_wire_off, c->enc, c->d_err))
+        return rc;
+    return scratch_leave(c->enc_order, s, ordered);
+}
+
+namespace {
+
+// One fan-out message's k frames on the flat / piece kernels (frame sizes the
+// period path does not take).
+int fanout_one_flat(wsg_ctx* c, hipStream_t s, const uint8_t* d_payload, uint64_t len, const uint32_t* d_keys,
+                    uint32_t k, uint8_t opcode, int mask, uint8_t* d_wire)
+{
+    const uint64_t fsize = wsg_frame_size(opcode, mask, len, 0);
+    const uint64_t total = fsize * k;
+    const uint64_t blocks = ceil_div(ceil_div(total, wsg::CHUNK), wsg::BLOCK * wsg::FAN_UNITS);
+    WSG_HIP(wsg::launch_fanout(s, grid_for(c, blocks), d_payload, len, d_keys, k, opcode, mask ? 1u : 0u, fsize,
+                               d_wire));
+    return WSG_OK;
+}
+
+// m messages x k keys.  Messages of one geometry (length, opcode) whose frame
+// size suits the period kernel go FAN_MSGS at a time into one launch
+// (blockIdx.y = message); the others take one flat launch each.
+int fanout_many(wsg_ctx* c, hipStream_t s, const uint8_t* d_payload, const uint64_t* src_off, const uint64_t* len,
+                const uint8_t* opcode, uint32_t m, const uint32_t* d_keys, uint32_t k, int mask, uint8_t* d_wire,
+                const uint64_t* wire_off)
+{
+    std::vector<char> done(m, 0);
+    for (uint32_t i = 0; i < m; ++i) {
+        if (done[i])
+            continue;
+        const uint64_t fsize = wsg_frame_size(opcode[i], mask, len[i], 0);
+        wsg::FanMsgs g{};
+        uint32_t cnt = 0;
+        std::vector<uint32_t> members;
+        for (uint32_t q = i; q < m; ++q) {
+            if (done[q] || len[q] != len[i] || opcode[q] != opcode[i])
+                continue;
+            members.push_back(q);
+        }
+        for (size_t at = 0; at < members.size(); at += wsg::FAN_MSGS) {
+            cnt = uint32_t(std::min<size_t>(wsg::FAN_MSGS, members.size() - at));
+            for (uint32_t q = 0; q < cnt; ++q) {
+                g.src[q] = src_off[members[at + q]];
+                g.dst[q] = wire_off[members[at + q]];
+            }
+            hipError_t perr = hipSuccess;
+            if (wsg::launch_fanout_period(s, c->num_cus, c->fan_waves_per_cu, c->fan_wpb, d_payload, len[i], d_keys, k, opcode[i],
+                                          mask ? 1u : 0u, fsize, d_wire, g, cnt, &perr)) {
+                WSG_HIP(perr);
+            } else {
+                for (uint32_t q = 0; q < cnt; ++q)
+                    if (int rc = fanout_one_flat(c, s, d_payload + g.src[q], len[i], d_keys, k, opcode[i], mask,
+                                                 d_wire + g.dst[q]))
+                        return rc;
+            }
+        }
+        for (uint32_t q : members)
+            done[q] = 1;
+    }
+    return WSG_OK;
+}
+
+} // namespace
+
+int wsg_fanout_encode(wsg_ctx* c, const uint8_t* d_payload, uint64_t len, const uint32_t* d_keys, uint32_t k,
+                      uint8_t opcode, int mask, uint8_t* d_wire, uint64_t wire_cap, void* stream)
+{
+    if (!c || (k && (!d_keys || !d_wire)) || (len && !d_payload))
+        return WSG_EINVAL;
+    if (!aligned16(d_wire))
+        return WSG_EINVAL;
+    if (k == 0)
+        return WSG_OK;
+    const uint64_t total = wsg_frame_size(opcode, mask, len, 0) * k;
+    if (total > wire_cap)
+        return WSG_ENOMEM;
+    if (c->check && (!in_alloc(d_payload, len) || !in_alloc(d_keys, uint64_t(k) * 4) || !in_alloc(d_wire, total)))
+        return WSG_EINVAL;
+    hipStream_t s = as_stream(stream);
+    const uint64_t src = 0, off[2] = {0, total};
+    const int t = timing_begin(c, s);
+    if (int rc = fanout_many(c, s, d_payload, &src, &len, &opcode, 1, d_keys, k, mask, d_wire, off))
+        return rc;
+    timing_end(c, s, t);
+    return WSG_OK;
+}
+
+int wsg_fanout_encode_many(wsg_ctx* c, const uint8_t* d_payload, const uint64_t* src_off, const uint64_t* len,
+                           const uint8_t* opcode, uint32_t m, const uint32_t* d_keys, uint32_t k, int mask,
+                           uint8_t* d_wire, uint64_t wire_cap, uint64_t* wire_off, void* stream)
+{
+    try {   // no C++ exception leaves the ABI (host vectors: WSG_ENOMEM)
+        if (!c || !wire_off || (m && (!src_off || !len || !opcode)) || (m && k && (!d_keys || !d_wire)))
+            return WSG_EINVAL;
+        if (d_wire && !aligned16(d_wire))
+            return WSG_EINVAL;
+        // message i's frames from wire_off[i], line-aligned (whole-line store rows)
+        uint64_t at = 0;
+        bool any_payload = false;
+        for (uint32_t i = 0; i < m; ++i) {
+            at = (at + wsg::PIECE_ALIGN - 1) & ~(wsg::PIECE_ALIGN - 1);
+            wire_off[i] = at;
+            at += wsg_frame_size(opcode[i], mask, len[i], 0) * k;
+            any_payload = any_payload || len[i] != 0;
+        }
+        wire_off[m] = at;
+        if (at > wire_cap)
+            return WSG_ENOMEM;
+        if (m == 0 || k == 0)
+            return WSG_OK;
+        if (any_payload && !d_payload)
+            return WSG_EINVAL;
+        if (c->check) {
+            if (!in_alloc(d_keys, uint64_t(k) * 4) || !in_alloc(d_wire, at))
+                return WSG_EINVAL;
+            for (uint32_t i = 0; i < m; ++i)
+                if (len[i] && !in_alloc(d_payload + src_off[i], len[i]))
+                    return WSG_EINVAL;
+        }
+        hipStream_t s = as_stream(stream);
+        const int t = timing_begin(c, s);
+        if (int rc = fanout_many(c, s, d_payload, src_off, len, opcode, m, d_keys, k, mask, d_wire, wire_off))
+            return rc;
+        timing_end(c, s, t);
+        return WSG_OK;
+    } catch (...) {
+        return WSG_ENOMEM;
+    }
+}

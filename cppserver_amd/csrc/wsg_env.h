@@ -5,7 +5,7 @@
 // creating their codec contexts at once crashed in getenv inside wsg_create
 // (tools/calls_r4/gpu_r4ah.sh, backtrace in profiles/r4/getenv_race.log).
 // So every read goes through env() under one lock, and the library's first
-// HIP call (hip_init_once, wsg_capi.hip) and context creation (wsg_create,
+// HIP call (hip_init_once, wsg_capi.cpp) and context creation (wsg_create,
 // whose HIP calls may initialize the device) run under the same lock.
 #pragma once
 
@@ -42,7 +42,7 @@ inline const char* envp(const char* name)
 }
 
 // The HIP runtime initialized once, under env_mutex (its environment edits
-// then never overlap an env() on another thread).  Defined in wsg_capi.hip.
+// then never overlap an env() on another thread).  Defined in wsg_capi.cpp.
 void hip_init_once();
 
 } // namespace wsg

@@ -1,9 +1,10 @@
 // wsg_internal.h — kernel geometry and kernel declarations shared by the
 // kernel sources (wsg_kernels.hip, wsg_messages.hip, wsg_frames.hip,
-// wsg_utf8.hip, wsg_proto.hip) and the C-ABI implementation.
+// wsg_utf8.hip, wsg_proto.hip) and the C-ABI implementation (wsg_ctx.h).
 #pragma once
 
 #include "wsg_frame.h"
+#include "wsg_lane_plan.h"   // LANE_THREADS, LANE_GROUPS_MAX
 
 namespace wsg {
 
@@ -284,7 +285,6 @@ hipError_t launch_test_spin(hipStream_t s, uint32_t us);
 // resumes each mailbox where the last one left it (next_j).
 enum : uint32_t { LANE_DECODE = 1, LANE_ENCODE = 2, LANE_XOR = 3, LANE_XOR_INLINE = 4 };
 constexpr uint64_t LANE_INLINE = 40;     // xor: payloads up to this size travel in the task (w[4..8])
-constexpr uint32_t LANE_THREADS = 1024;   // one workgroup; frames per group (lane per frame)
 constexpr uint64_t LANE_STAGE = 64 << 10;  // decode: wire bytes staged in LDS (one group's range limit)
 constexpr uint64_t LANE_PSTAGE = 64 << 10; // encode: payload arena staged in LDS when its 16-B blocks fit
 // LDS of the lane (one layout per op, the larger sized):
@@ -295,7 +295,6 @@ constexpr uint64_t LANE_LDS_ENCODE = 72 * LANE_THREADS + 64 + LANE_PSTAGE;
 constexpr uint64_t LANE_LDS = LANE_LDS_DECODE > LANE_LDS_ENCODE ? LANE_LDS_DECODE : LANE_LDS_ENCODE;
 static_assert(LANE_LDS <= 160 * 1024 - 1024, "the lane's workgroup LDS");
 constexpr uint32_t LANE_WGS_MAX = 32;          // workgroups of the lane (each a CU's worth of LDS)
-constexpr uint32_t LANE_GROUPS_MAX = 32;       // frame groups of a request (<= 32 Ki frames)
 constexpr uint32_t LANE_RING = 64;             // task slots per workgroup mailbox
 constexpr uint32_t LANE_WORDS = 9;             // task units (w[])
 // A task word and the ticket it belongs to, + 1 (the host stores v, then
@@ -355,10 +354,5 @@ struct LaneBell {
 // their first poll (a lane that starts late).
 hipError_t launch_lane(hipStream_t s, LaneBell* bell, uint32_t workgroups, uint64_t idle_ticks,
                        uint64_t yield_ticks, uint32_t gen, uint64_t delay_ticks);
-
-// HIP device a context is bound to (wsg_capi.hip)
-int ctx_device(const wsg_ctx* c);
-// $WSG_HOST_MULTI_SHARE as the context read it at wsg_create (wsg_mgpu.cpp)
-bool ctx_multi_share(const wsg_ctx* c);
 
 } // namespace wsg

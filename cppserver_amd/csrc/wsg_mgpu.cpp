@@ -23,7 +23,7 @@
 // RCCL is loaded at run time (dlopen, RTLD_LOCAL) from $WSG_RCCL_LIB or the
 // ROCm install, so that a host process which already carries another RCCL
 // (PyTorch bundles one) keeps the two apart.
-#include "wsg_internal.h"
+#include "wsg_ctx.h"
 #include "wsg_env.h"
 #include "wsg_trace.h"
 
@@ -202,7 +202,7 @@ void on_contexts(wsg_ctx* const* ctxs, int parts, Fn fn)
     for (int i = 1; i < parts; ++i) {
         try {
             th.emplace_back([&, i] {
-                (void)hipSetDevice(wsg::ctx_device(ctxs[i]));
+                (void)hipSetDevice(ctxs[i]->device);
                 fn(i);
             });
         } catch (...) {
@@ -211,10 +211,10 @@ void on_contexts(wsg_ctx* const* ctxs, int parts, Fn fn)
     }
     int prev = 0;
     (void)hipGetDevice(&prev);
-    (void)hipSetDevice(wsg::ctx_device(ctxs[0]));
+    (void)hipSetDevice(ctxs[0]->device);
     fn(0);
     for (int i : inline_parts) {
-        (void)hipSetDevice(wsg::ctx_device(ctxs[i]));
+        (void)hipSetDevice(ctxs[i]->device);
         fn(i);
     }
     (void)hipSetDevice(prev);
@@ -229,11 +229,11 @@ void on_contexts(wsg_ctx* const* ctxs, int parts, Fn fn)
 // context (the one-GPU tests exercise the split that way).
 std::vector<wsg_ctx*> one_per_device(wsg_ctx* const* ctxs, int nctx)
 {
-    const bool share = nctx > 0 && wsg::ctx_multi_share(ctxs[0]);   // (read at wsg_create, not per call)
+    const bool share = nctx > 0 && ctxs[0]->multi_share;   // (read at wsg_create, not per call)
     std::vector<wsg_ctx*> v;
     std::vector<int> seen;
     for (int i = 0; i < nctx; ++i) {
-        const int d = wsg::ctx_device(ctxs[i]);
+        const int d = ctxs[i]->device;
         if (!share && std::find(seen.begin(), seen.end(), d) != seen.end())
             continue;
         seen.push_back(d);

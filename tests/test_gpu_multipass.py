@@ -245,3 +245,52 @@ def test_encode_piece_scan_three_passes(codecs):
         assert np.array_equal(off.cpu().numpy().view(np.uint64), off_o), cap
         assert np.array_equal(wire[:exact].cpu().numpy(), wire_o), cap
         del wire
+
+
+# ------------------------------- staged host pipelines, slot buffers regrown
+@functools.lru_cache(maxsize=None)
+def _growth_batches():
+    """Three batches whose segments (1 MiB) ask the slots for different
+    buffers in turn: (payload, desc, oracle's wire and offsets, oracle's decode)."""
+    rng = np.random.default_rng(51)
+    out = []
+    for lo, hi, nbytes in ((1010, 1018, 5 << 19),       # ~2.5 MiB of ~1 KiB frames
+                           (65000, 65528, 5 << 20),     # more bytes, fewer frames per segment
+                           (8, 14, 3 << 19)):           # ~1.5 MiB of ~20-byte frames: more frames, fewer bytes
+        lens = rng.integers(lo, hi + 1, nbytes // ((lo + hi) // 2 + 6))
+        desc, total = wl.ragged_desc(rng, lens)
+        desc["mask"] = rng.random(len(desc)) < 0.8
+        payload = wl.random_bytes(rng, total)
+        wire, off = oracle.encode_batch(payload, desc)
+        out.append((payload, desc, wire, off, oracle.decode_batch(wire, off[:-1].copy())))
+    return out
+
+
+def test_host_pipeline_slot_buffers_regrow(monkeypatch):
+    """One context ($WSG_STAGE_MB=1, pageable buffers): three staged decodes,
+    then three staged encodes, each asking the slots for larger byte buffers
+    and smaller frame tables than the call before it, or the reverse, so every
+    slot array is freed and regrown between calls; the context destroyed at
+    the end.  Every call's bytes, records and offsets equal the oracle's."""
+    batches = _growth_batches()
+    per_seg = [(len(w) / -(-len(w) // (1 << 20)), len(d) / -(-len(w) // (1 << 20))) for _, d, w, _, _ in batches]
+    assert per_seg[1][0] >= per_seg[0][0] and per_seg[1][1] < per_seg[0][1]   # more bytes, fewer frames
+    assert per_seg[2][1] > 4 * per_seg[0][1]                                  # more frames than any before
+    monkeypatch.setenv("WSG_STAGE_MB", "1")   # (read at wsg_create; put back after the test)
+    c = ca.Codec(0)
+    try:
+        for payload, desc, wire, off, ref in batches:
+            assert len(wire) > (1 << 20) and ref[0] == 0   # the staged pipeline, more than one segment
+            out = np.full(len(wire) + PAD, SENTINEL, dtype=np.uint8)
+            rc, got, info = c.decode_batch_host(np.array(wire), off[:-1].copy(), out=out)
+            _check(rc, got, info, ref)
+            assert (out[len(wire):] == SENTINEL).all()
+        for payload, desc, wire, off, _ in batches:
+            buf = np.full(len(wire) + PAD, SENTINEL, dtype=np.uint8)
+            rc, got, got_off = c.encode_batch_host(payload, desc, wire=buf)
+            assert rc == 0
+            assert np.array_equal(got_off, off)
+            assert np.array_equal(got, wire)
+            assert (buf[len(wire):] == SENTINEL).all()
+    finally:
+        c.close()

@@ -6,7 +6,8 @@ drop-in compile check (CPU only, no GPU).
   and runs a randomized driver over them (tests/cpp/test_host_sanitize.cpp:
   round trips, split streams, garbage streams and frame tables, mutated HTTP
   requests), and the handshake test with the product's host sources
-  (ws.cpp, ws_api.cpp, ws_batch.cpp, http.cpp) instrumented;
+  (ws.cpp, ws_api.cpp, ws_batch.cpp, http.cpp) instrumented, and the lane's
+  group planner over enumerated small requests (tests/cpp/test_lane_plan.cpp);
 * `make -C tests/cpp threads` builds the batches' cross-thread test
   (tests/cpp/test_batch_threads.cpp) with the product's host sources under
   ThreadSanitizer and under AddressSanitizer;
@@ -44,6 +45,15 @@ def test_sanitized_oracle_and_http():
 def test_sanitized_handshake():
     _make("sanitize")
     _run(os.path.join(CPP, "_build", "san", "test_handshake"))
+
+
+def test_sanitized_lane_plan():
+    """The lane's group planner (lane_plan, cppserver_amd/csrc/wsg_lane_plan.h):
+    groups contiguous over [0, n), 1..LANE_THREADS frames each, their byte
+    ranges within the limit, at most LANE_GROUPS_MAX; the requests it must
+    refuse (tests/cpp/test_lane_plan.cpp)."""
+    _make("sanitize")
+    _run(os.path.join(CPP, "_build", "san", "test_lane_plan"))
 
 
 def test_batch_threads_tsan():

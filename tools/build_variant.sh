@@ -1,6 +1,7 @@
 #!/bin/bash
 # Build an A/B variant of libwsg.so with extra -D flags into cppserver_amd/_build/var/<name>/.
-#   tools/build_variant.sh NAME [-DFOO=1 ...]     ($KSRC / $CSRC: another wsg_kernels.hip / wsg_capi.hip, e.g. an older revision;
+#   tools/build_variant.sh NAME [-DFOO=1 ...]     ($KSRC: another wsg_kernels.hip, e.g. an older revision; $CSRC: other C-ABI
+#   sources in place of wsg_capi.cpp wsg_lane.cpp wsg_capi_device.cpp wsg_capi_host.cpp, e.g. an older wsg_capi.hip;
 #   $PSRC: the pipeline kernel sources, "" for a wsg_kernels.hip from before they left it)
 set -e
 name=$1; shift
@@ -18,7 +19,12 @@ for p in ${PSRC-$csrc/wsg_messages.hip $csrc/wsg_frames.hip $csrc/wsg_utf8.hip $
     $H $F -I$csrc -c "$p" -o "$o"
     pobjs="$pobjs $o"
 done
-$H $F -I$csrc -c ${CSRC:-$csrc/wsg_capi.hip} -o c.o
+cobjs=
+for c in ${CSRC-$csrc/wsg_capi.cpp $csrc/wsg_lane.cpp $csrc/wsg_capi_device.cpp $csrc/wsg_capi_host.cpp}; do
+    o=c_$(basename "${c%.*}").o
+    case $c in *.hip) $H $F -I$csrc -c "$c" -o "$o" ;; *) $H -O3 -std=c++17 -fPIC -I$root/include $* -I$csrc -c "$c" -o "$o" ;; esac
+    cobjs="$cobjs $o"
+done
 $H -O3 -std=c++17 -fPIC -I$root/include -c $root/cppserver_amd/csrc/ws.cpp -o w.o
 $H -O3 -std=c++17 -fPIC -I$root/include -c $root/cppserver_amd/csrc/ws_api.cpp -o a.o
 $H -O3 -std=c++17 -fPIC -I$root/include -c $root/cppserver_amd/csrc/ws_batch.cpp -o b.o
@@ -27,5 +33,5 @@ $H -O3 -std=c++17 -fPIC -I$root/include -c $root/cppserver_amd/csrc/tls.cpp -o t
 $H -O3 -std=c++17 -fPIC -I$root/include -c $root/cppserver_amd/csrc/wss.cpp -o s.o
 $H -O3 -std=c++17 -fPIC -I$root/include -c $root/cppserver_amd/csrc/wsg_mgpu.cpp -o m.o
 $H -O3 -std=c++17 -fPIC -I$root/include -c $root/cppserver_amd/csrc/wsg_proto_host.cpp -o j.o
-$H --offload-arch=gfx950 -shared -o libwsg.so k.o $pobjs c.o w.o a.o b.o h.o t.o s.o m.o j.o -lssl -lcrypto -ldl -L/opt/rocm/lib -lrocprofiler-sdk-roctx
+$H --offload-arch=gfx950 -shared -o libwsg.so k.o $pobjs $cobjs w.o a.o b.o h.o t.o s.o m.o j.o -lssl -lcrypto -ldl -L/opt/rocm/lib -lrocprofiler-sdk-roctx
 echo "$out/libwsg.so"

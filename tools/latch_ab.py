@@ -1,8 +1,8 @@
 """Host batch decode time per call for the status-pass shapes: many small
 frames in place (page-locked, one k_decode launch) and staged (pageable,
 the segmented pipeline), and C2's 4096 x 64 KiB staged, through the product
-library or a variant (tools/build_variant.sh; e.g. one built from an older
-wsg_capi.hip with $CSRC).  One library per process.  Diagnostic only.
+library or a variant (tools/build_variant.sh; e.g. one built from older
+C-ABI sources with $CSRC).  One library per process.  Diagnostic only.
 usage: python tools/latch_ab.py [LIB] [CALLS=20]   (prints one JSON line)"""
 import json
 import os
