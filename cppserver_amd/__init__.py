@@ -20,7 +20,7 @@ from .layout import (  # noqa: F401  (re-exported)
     reply_plan, utf8_plan,
     PROTO_ANY, PROTO_CLIENT, PROTO_SERVER, PROTO_STATE, PROTO_VERDICT, PV_CLOSE_CODE, PV_CLOSE_LEN, PV_CLOSED, PV_CONT,
     PV_CTRL_FRAGMENT, PV_CTRL_LONG, PV_DATA, PV_FRAME, PV_MASK, PV_NONE, PV_OPCODE, PV_RSV, PV_TOO_BIG, protocol_plan,
-    PV_UTF8, checked_reply_plan, merge_verdicts, utf8_verdicts,
+    PV_UTF8, checked_reply_plan, merge_verdicts, utf8_verdicts, utf8_wire_plan, validated_verdicts,
 )
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -76,7 +76,12 @@ def lib(path=None):
                                    vp, vp, vp, vp, vp, vp]),
         "wsg_reply_checked_streams": (ci, [vp, vp, u64, vp, u32, vp, vp, u32, vp, vp, u32, u64, vp, ci, vp, vp, u64, vp,
                                            vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(u32), vp]),
+        "wsg_reply_validated": (ci, [vp, vp, u64, vp, u32, vp, u32, vp, vp, u32, u64, vp, u32, vp, ci, vp, vp, u64, vp,
+                                     vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "wsg_reply_validated_streams": (ci, [vp, vp, u64, vp, u32, vp, vp, u32, vp, vp, u32, u64, u32, vp, ci, vp, vp,
+                                             u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(u32), vp]),
         "wsg_utf8_verdicts": (ci, [vp, vp, vp, u32, u32, vp, u32, vp, vp]),
+        "wsg_check_utf8_wire": (ci, [vp, vp, u64, vp, u32, vp, u32, vp, u32, vp, vp, vp, vp, vp, vp]),
         "wsg_check_utf8": (ci, [vp, vp, u64, vp, vp, u32, u32, vp, vp, vp]),
         "wsg_utf8_valid_up_to": (u64, [vp, u64]),
         "wsg_check_protocol": (ci, [vp, vp, u64, vp, u32, vp, u32, vp, vp, u32, u64, vp, vp, vp]),
@@ -366,6 +371,45 @@ class Codec:
                                     self._stream(stream))
         _check(rc, "wsg_check_utf8")
         return valid, result
+
+    def check_utf8_wire(self, wire, frame_start, stream_first, state=None, which=UTF8_TEXT | UTF8_CLOSE, msgs=None,
+                        count=None, info=None, valid=None, result=None, stream=None):
+        """wsg_check_utf8_wire: check_utf8 over the messages of a frame table,
+        read from the masked wire (no message buffer).  ``wire`` /
+        ``frame_start`` / ``stream_first`` / ``state`` as decode_messages, but
+        ``state`` is only read.  Returns (valid, result, msgs, count, info):
+        valid int64[n] and result int64[4] as check_utf8 returns them for the
+        dense layout of the same messages, and the MSG table bytes, count
+        int64[2] and the RECV_INFO bytes as decode_messages writes them."""
+        t = self._torch
+        n = int(frame_start.numel())
+        ns = int(stream_first.numel()) - 1
+        if ns < 0 or stream_first.element_size() != 4:
+            raise WSGError(WSG_EINVAL, "check_utf8_wire: stream_first must hold n_streams + 1 32-bit indices")
+        dev = wire.device
+        if state is None:
+            state = t.zeros(max(ns, 1) * STREAM_STATE.itemsize, dtype=t.uint8, device=dev)
+        if msgs is None:
+            msgs = t.empty(max(n, 1) * MSG.itemsize, dtype=t.uint8, device=dev)
+        if count is None:
+            count = t.empty(2, dtype=t.int64, device=dev)
+        if info is None:
+            info = t.empty(max(n, 1) * RECV_INFO.itemsize, dtype=t.uint8, device=dev)
+        if valid is None:
+            valid = t.empty(max(n, 1), dtype=t.int64, device=dev)
+        if result is None:
+            result = t.empty(4, dtype=t.int64, device=dev)
+        if (int(state.numel()) < ns * STREAM_STATE.itemsize or int(msgs.numel()) < n * MSG.itemsize
+                or int(info.numel()) < n * RECV_INFO.itemsize or int(count.numel()) < 2 or count.element_size() != 8
+                or valid.element_size() != 8 or int(result.numel()) < 4 or result.element_size() != 8):
+            raise WSGError(WSG_EINVAL, "check_utf8_wire: a buffer is smaller than the batch needs")
+        p = ctypes.c_void_p
+        rc = self._L.wsg_check_utf8_wire(self._ctx, p(wire.data_ptr()), wire.numel(), p(frame_start.data_ptr()), n,
+                                         p(stream_first.data_ptr()), ns, p(state.data_ptr()), int(which),
+                                         p(msgs.data_ptr()), p(count.data_ptr()), p(info.data_ptr()),
+                                         p(valid.data_ptr()), p(result.data_ptr()), self._stream(stream))
+        _check(rc, "wsg_check_utf8_wire")
+        return valid, result, msgs, count, info
 
     # -- the frame-sequence rules of RFC 6455 ----------------------------------
     def check_protocol(self, wire, info, n, stream_first, proto=None, role=PROTO_ANY, max_message=0, state=None,
@@ -668,6 +712,86 @@ class Codec:
         _check(rc, "wsg_reply_checked_streams")
         return (reply, reply_off, stream_reply, close_off, verdict, proto, result, msgs, count, state, info,
                 frame_start, stream_first, n.value)
+
+    # -- validated replies (reply_checked with check_utf8_wire inside it) -------
+    def _validated_args(self, what, dev, n, valid, utf8_result):
+        t = self._torch
+        if valid is None:
+            valid = t.empty(max(n, 1), dtype=t.int64, device=dev)
+        if utf8_result is None:
+            utf8_result = t.empty(4, dtype=t.int64, device=dev)
+        if (int(valid.numel()) < n or valid.element_size() != 8 or int(utf8_result.numel()) < 4
+                or utf8_result.element_size() != 8):
+            raise WSGError(WSG_EINVAL, "%s: a buffer is smaller than the batch needs" % what)
+        return valid, utf8_result
+
+    def reply_validated(self, wire, frame_start, stream_first, proto=None, role=PROTO_ANY, max_message=0, also=None,
+                        which=UTF8_TEXT | UTF8_CLOSE, reply_op=ECHO_REPLY, mask=False, send_keys=None, state=None,
+                        reply=None, reply_cap=None, stream=None, reply_off=None, stream_reply=None, close_off=None,
+                        verdict=None, result=None, valid=None, utf8_result=None, msgs=None, count=None, info=None):
+        """wsg_reply_validated: reply_checked with the UTF-8 check of
+        check_utf8_wire inside it; a stream whose text message or close
+        reason is invalid gets the 1007 close frame at that message's FIN
+        frame.  Arguments as reply_checked, and ``which`` (UTF8_* bits).
+        Returns reply_checked's tuple followed by (valid, utf8_result) as
+        check_utf8_wire returns them."""
+        n = int(frame_start.numel())
+        ns = int(stream_first.numel()) - 1
+        if ns < 0 or stream_first.element_size() != 4:
+            raise WSGError(WSG_EINVAL, "reply_validated: stream_first must hold n_streams + 1 32-bit indices")
+        proto, close_off, verdict, result, count = self._checked_args("reply_validated", wire.device, ns, proto,
+                                                                      close_off, verdict, result, count)
+        if also is not None and int(also.numel()) * also.element_size() < ns * PROTO_VERDICT.itemsize:
+            raise WSGError(WSG_EINVAL, "reply_validated: also must hold n_streams verdicts")
+        valid, utf8_result = self._validated_args("reply_validated", wire.device, n, valid, utf8_result)
+        rule, cap, reply, reply_off, stream_reply, state, msgs, count, info = self._reply_args(
+            "reply_validated", wire, n, ns, reply_op, send_keys, reply, reply_cap, reply_off, stream_reply, state,
+            msgs, count, info)
+        p = ctypes.c_void_p
+        rc = self._L.wsg_reply_validated(self._ctx, p(wire.data_ptr()), wire.numel(), p(frame_start.data_ptr()), n,
+                                         p(stream_first.data_ptr()), ns, p(state.data_ptr()), p(proto.data_ptr()),
+                                         int(role), int(max_message), p(also.data_ptr()) if also is not None else None,
+                                         int(which), rule, 1 if mask else 0,
+                                         p(send_keys.data_ptr()) if send_keys is not None else None,
+                                         p(reply.data_ptr()), cap, p(reply_off.data_ptr()),
+                                         p(stream_reply.data_ptr()), p(close_off.data_ptr()), p(verdict.data_ptr()),
+                                         p(result.data_ptr()), p(valid.data_ptr()), p(utf8_result.data_ptr()),
+                                         p(msgs.data_ptr()), p(count.data_ptr()), p(info.data_ptr()),
+                                         self._stream(stream))
+        _check(rc, "wsg_reply_validated")
+        return (reply, reply_off, stream_reply, close_off, verdict, proto, result, msgs, count, state, info, valid,
+                utf8_result)
+
+    def reply_validated_streams(self, wire, spans, proto=None, role=PROTO_ANY, max_message=0,
+                                which=UTF8_TEXT | UTF8_CLOSE, reply_op=ECHO_REPLY, mask=False, send_keys=None,
+                                state=None, frame_start=None, frame_cap=None, stream_first=None, reply=None,
+                                reply_cap=None, stream=None, reply_off=None, stream_reply=None, close_off=None,
+                                verdict=None, result=None, valid=None, utf8_result=None, msgs=None, count=None,
+                                info=None):
+        """wsg_reply_validated_streams: reply_checked_streams with
+        reply_validated in the middle.  Returns reply_validated's tuple
+        followed by (frame_start, stream_first, n_frames)."""
+        ns, fcap, frame_start, stream_first = self._frame_args("reply_validated_streams", wire, spans, frame_start,
+                                                               frame_cap, stream_first)
+        proto, close_off, verdict, result, count = self._checked_args("reply_validated_streams", wire.device, ns,
+                                                                      proto, close_off, verdict, result, count)
+        valid, utf8_result = self._validated_args("reply_validated_streams", wire.device, fcap, valid, utf8_result)
+        rule, cap, reply, reply_off, stream_reply, state, msgs, count, info = self._reply_args(
+            "reply_validated_streams", wire, fcap, ns, reply_op, send_keys, reply, reply_cap, reply_off, stream_reply,
+            state, msgs, count, info)
+        n = ctypes.c_uint32()
+        p = ctypes.c_void_p
+        rc = self._L.wsg_reply_validated_streams(
+            self._ctx, p(wire.data_ptr()), wire.numel(), p(spans.data_ptr()), ns, p(state.data_ptr()),
+            p(frame_start.data_ptr()), fcap, p(stream_first.data_ptr()), p(proto.data_ptr()), int(role),
+            int(max_message), int(which), rule, 1 if mask else 0,
+            p(send_keys.data_ptr()) if send_keys is not None else None, p(reply.data_ptr()), cap,
+            p(reply_off.data_ptr()), p(stream_reply.data_ptr()), p(close_off.data_ptr()), p(verdict.data_ptr()),
+            p(result.data_ptr()), p(valid.data_ptr()), p(utf8_result.data_ptr()), p(msgs.data_ptr()),
+            p(count.data_ptr()), p(info.data_ptr()), ctypes.byref(n), self._stream(stream))
+        _check(rc, "wsg_reply_validated_streams")
+        return (reply, reply_off, stream_reply, close_off, verdict, proto, result, msgs, count, state, info, valid,
+                utf8_result, frame_start, stream_first, n.value)
 
     def utf8_verdicts(self, msgs, count, valid, n_streams, which=UTF8_TEXT | UTF8_CLOSE, msg_room=None, also=None,
                       stream=None):

@@ -135,6 +135,8 @@ void read_knobs(wsg_ctx* c)
         c->dec_blocks_per_cu = int(ranged(e, 1, 4096, c->dec_blocks_per_cu));
     if (const char* e = wsg::envp("WSG_UTF8_BLOCKS_PER_CU"))
         c->utf8_blocks_per_cu = int(ranged(e, 1, 4096, c->utf8_blocks_per_cu));
+    if (const char* e = wsg::envp("WSG_UTF8_WIRE_BLOCKS_PER_CU"))
+        c->utf8_wire_blocks_per_cu = int(ranged(e, 1, 4096, c->utf8_wire_blocks_per_cu));
     if (const char* e = wsg::envp("WSG_HOST_MULTI_SHARE"))
         c->multi_share = *e == '1';
 }

@@ -52,12 +52,24 @@ int msg_scratch(wsg_ctx* c, hipStream_t s, uint32_t n, uint64_t wire_len, wsg::M
 
 // The scratch of wsg_check_protocol / wsg_reply_checked for n frames in
 // n_streams streams: the plan block, the context's, entered as msg_scratch's.
-int proto_scratch(wsg_ctx* c, hipStream_t s, uint32_t n, uint32_t n_streams, wsg::ProtoPlan* plan, bool* ordered)
+// `also` (wsg_reply_validated): n_streams more words behind that block, the
+// merged verdicts its reply kernels read, under the same order.
+int proto_scratch(wsg_ctx* c, hipStream_t s, uint32_t n, uint32_t n_streams, wsg::ProtoPlan* plan, bool* ordered,
+                  uint64_t** also = nullptr)
 {
-    if (int rc = ensure_array(c->d_proto_plan, c->proto_plan_cap, wsg::proto_plan_layout(nullptr, n, n_streams, nullptr)))
+    const uint64_t block = (wsg::proto_plan_layout(nullptr, n, n_streams, nullptr) + 15) & ~uint64_t(15);
+    if (int rc = ensure_array(c->d_proto_plan, c->proto_plan_cap, block + (also ? uint64_t(n_streams) * 8 : 0)))
         return rc;
     wsg::proto_plan_layout(c->d_proto_plan, n, n_streams, plan);
+    if (also)
+        *also = reinterpret_cast<uint64_t*>(c->d_proto_plan + block);
     return scratch_enter(c->proto_order, s, ordered);
+}
+
+// k_utf8_wire: a wave per piece record, under a cap of its own.
+int utf8_wire_grid(const wsg_ctx* c, uint64_t pieces_cap)
+{
+    return grid_for(c, ceil_div(pieces_cap, wsg::BLOCK / 64), c->utf8_wire_blocks_per_cu);
 }
 
 wsg::ReplyRule make_rule(const uint8_t reply_op[5], int mask)
@@ -158,6 +170,51 @@ int wsg_check_utf8(wsg_ctx* c, const uint8_t* d_msg, uint64_t msg_cap, const wsg
     }
     WSG_HIP(wsg::launch_utf8_count(s, rec_grid, d_msgs, d_count, msg_room, msg_cap, which, d_valid, d_result));
     return WSG_OK;
+}
+
+// wsg_check_utf8 with the message plan in front of it and the wire in the
+// place of d_msg: the plan up to the piece records (d_state only read), the
+// per-record kernels around the payload kernel, which reads every delivered
+// payload byte once where it lies.
+int wsg_check_utf8_wire(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const uint64_t* d_frame_start,
+                        uint32_t n, const uint32_t* d_stream_first, uint32_t n_streams,
+                        const wsg_stream_state* d_state, uint32_t which, wsg_msg* d_msgs, uint64_t* d_count,
+                        wsg_recv_info* d_info, uint64_t* d_valid, uint64_t* d_result, void* stream)
+{
+    if (!c || !d_count || !d_result || !d_stream_first || (wire_len && !d_wire) ||
+        (n && (!d_frame_start || !d_info || !d_msgs || !d_valid || n_streams == 0)) || (n_streams && !d_state) ||
+        n == UINT32_MAX || n_streams == UINT32_MAX)
+        return WSG_EINVAL;
+    if (!aligned16(d_wire) || !aligned8(d_frame_start) || (reinterpret_cast<uintptr_t>(d_stream_first) & 3u) ||
+        !aligned8(d_state) || !aligned8(d_msgs) || !aligned8(d_count) || !aligned8(d_info) || !aligned8(d_valid) ||
+        !aligned8(d_result))
+        return WSG_EINVAL;
+    if (c->check &&
+        (!in_alloc(d_wire, (wire_len + 15) & ~uint64_t(15)) || !in_alloc(d_frame_start, uint64_t(n) * 8) ||
+         !in_alloc(d_stream_first, (uint64_t(n_streams) + 1) * 4) ||
+         !in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) ||
+         !in_alloc(d_msgs, uint64_t(n) * sizeof(wsg_msg)) || !in_alloc(d_count, 2 * 8) ||
+         !in_alloc(d_info, uint64_t(n) * sizeof(wsg_recv_info)) || !in_alloc(d_valid, uint64_t(n) * 8) ||
+         !in_alloc(d_result, 4 * 8)))
+        return WSG_EINVAL;
+    hipStream_t s = as_stream(stream);
+    wsg::MsgPlan plan;
+    uint64_t pieces_cap;
+    bool ordered = false;
+    if (int rc = msg_scratch(c, s, n, wire_len, &plan, &pieces_cap, &ordered))
+        return rc;
+    WSG_HIP(wsg::launch_msg_plan_only(s, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams, d_state,
+                                      d_msgs, d_count, d_info, plan, c->d_msg_pieces, pieces_cap, c->d_err));
+    const int rec_grid = grid_for(c, ceil_div(n, wsg::BLOCK));   // (at least one block: it seeds d_result)
+    WSG_HIP(wsg::launch_utf8_init(s, rec_grid, d_msgs, d_count, n, d_valid, d_result));
+    if (n && which) {
+        const int t = timing_begin(c, s);
+        WSG_HIP(wsg::launch_utf8_wire(s, utf8_wire_grid(c, pieces_cap), d_wire, wire_len, plan, c->d_msg_pieces,
+                                      pieces_cap, d_msgs, d_count, n, which, d_valid));
+        timing_end(c, s, t);
+    }
+    WSG_HIP(wsg::launch_utf8_count(s, rec_grid, d_msgs, d_count, n, UINT64_MAX, which, d_valid, d_result));
+    return scratch_leave(c->msg_order, s, ordered);
 }
 
 // The frame-sequence rules over a decoded batch: a scan of the frames' steps
@@ -354,14 +411,25 @@ int wsg_reply_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_
 // wsg_reply_messages with wsg_check_protocol inside it: the protocol kernels
 // run on the d_info the plan's header pass has just written, and the reply
 // kernels stop every stream at its terminal frame and close it there.
-int wsg_reply_checked(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const uint64_t* d_frame_start, uint32_t n,
-                      const uint32_t* d_stream_first, uint32_t n_streams, wsg_stream_state* d_state,
-                      wsg_proto_state* d_proto, uint32_t role, uint64_t max_message, const wsg_proto_verdict* d_also,
-                      const uint8_t reply_op[5], int mask, const uint32_t* d_send_key, uint8_t* d_reply,
-                      uint64_t reply_cap, uint64_t* d_reply_off, uint64_t* d_stream_reply, uint64_t* d_close_off,
-                      wsg_proto_verdict* d_verdict, uint64_t* d_result, wsg_msg* d_msgs, uint64_t* d_count,
-                      wsg_recv_info* d_info, void* stream)
+// `validated` (wsg_reply_validated): the UTF-8 check from the wire inside the
+// plan, d_valid and d_utf8_result written, its verdicts merged with d_also.
+namespace {
+
+int reply_checked(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const uint64_t* d_frame_start, uint32_t n,
+                  const uint32_t* d_stream_first, uint32_t n_streams, wsg_stream_state* d_state,
+                  wsg_proto_state* d_proto, uint32_t role, uint64_t max_message, const wsg_proto_verdict* d_also,
+                  const uint8_t reply_op[5], int mask, const uint32_t* d_send_key, uint8_t* d_reply,
+                  uint64_t reply_cap, uint64_t* d_reply_off, uint64_t* d_stream_reply, uint64_t* d_close_off,
+                  wsg_proto_verdict* d_verdict, uint64_t* d_result, wsg_msg* d_msgs, uint64_t* d_count,
+                  wsg_recv_info* d_info, void* stream, bool validated, uint32_t which, uint64_t* d_valid,
+                  uint64_t* d_utf8_result)
 {
+    if (validated) {
+        if (!d_utf8_result || (n && !d_valid) || !aligned8(d_valid) || !aligned8(d_utf8_result))
+            return WSG_EINVAL;
+        if (c && c->check && (!in_alloc(d_valid, uint64_t(n) * 8) || !in_alloc(d_utf8_result, 4 * 8)))
+            return WSG_EINVAL;
+    }
     if (!c || !d_count || !d_stream_first || !reply_op || !d_reply_off || !d_stream_reply || !d_close_off ||
         !d_proto || !d_verdict || !d_result || (wire_len && !d_wire) || (reply_cap && !d_reply) ||
         (n && (!d_frame_start || !d_info || !d_msgs || n_streams == 0)) || (n_streams && !d_state) ||
@@ -394,22 +462,59 @@ int wsg_reply_checked(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, cons
     wsg::MsgPlan plan;
     uint64_t pieces_cap;
     bool ordered = false, pordered = false;
-    if (int rc = proto_scratch(c, s, n, n_streams, &pplan, &pordered))
+    wsg::Utf8Inside utf8{which, d_valid, d_utf8_result, nullptr, 1, 1};
+    if (int rc = proto_scratch(c, s, n, n_streams, &pplan, &pordered, validated ? &utf8.also : nullptr))
         return rc;
     if (int rc = msg_scratch(c, s, n, wire_len, &plan, &pieces_cap, &ordered))
         return rc;
+    utf8.rec_grid = grid_for(c, ceil_div(n, wsg::BLOCK));
+    utf8.wire_grid = utf8_wire_grid(c, pieces_cap);
     WSG_HIP(wsg::launch_reply_checked_plan(s, grid_for(c, ceil_div(n_streams, wsg::BLOCK)), d_wire, wire_len,
                                            d_frame_start, n, d_stream_first, n_streams, d_state, d_proto, role,
                                            max_message, d_also, make_rule(reply_op, mask), d_send_key, d_reply,
                                            reply_cap, d_reply_off, d_stream_reply, d_close_off, d_verdict, d_result,
                                            d_msgs, d_count, d_info, plan, pplan, c->d_msg_pieces, pieces_cap,
-                                           c->d_err));
+                                           c->d_err, validated ? &utf8 : nullptr));
     if (n)
         if (int rc = gather_launch(c, s, wsg::launch_reply_gather, d_wire, plan, pieces_cap, d_reply, reply_cap))
             return rc;
     if (int rc = scratch_leave(c->proto_order, s, pordered))
         return rc;
     return scratch_leave(c->msg_order, s, ordered);
+}
+
+} // namespace
+
+int wsg_reply_checked(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const uint64_t* d_frame_start, uint32_t n,
+                      const uint32_t* d_stream_first, uint32_t n_streams, wsg_stream_state* d_state,
+                      wsg_proto_state* d_proto, uint32_t role, uint64_t max_message, const wsg_proto_verdict* d_also,
+                      const uint8_t reply_op[5], int mask, const uint32_t* d_send_key, uint8_t* d_reply,
+                      uint64_t reply_cap, uint64_t* d_reply_off, uint64_t* d_stream_reply, uint64_t* d_close_off,
+                      wsg_proto_verdict* d_verdict, uint64_t* d_result, wsg_msg* d_msgs, uint64_t* d_count,
+                      wsg_recv_info* d_info, void* stream)
+{
+    return reply_checked(c, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams, d_state, d_proto, role,
+                         max_message, d_also, reply_op, mask, d_send_key, d_reply, reply_cap, d_reply_off,
+                         d_stream_reply, d_close_off, d_verdict, d_result, d_msgs, d_count, d_info, stream, false, 0,
+                         nullptr, nullptr);
+}
+
+// wsg_reply_checked with wsg_check_utf8_wire and wsg_utf8_verdicts inside its
+// plan: one plan pass, the payload read once for the check and once for the
+// reply, written once.
+int wsg_reply_validated(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const uint64_t* d_frame_start,
+                        uint32_t n, const uint32_t* d_stream_first, uint32_t n_streams, wsg_stream_state* d_state,
+                        wsg_proto_state* d_proto, uint32_t role, uint64_t max_message, const wsg_proto_verdict* d_also,
+                        uint32_t which, const uint8_t reply_op[5], int mask, const uint32_t* d_send_key,
+                        uint8_t* d_reply, uint64_t reply_cap, uint64_t* d_reply_off, uint64_t* d_stream_reply,
+                        uint64_t* d_close_off, wsg_proto_verdict* d_verdict, uint64_t* d_result, uint64_t* d_valid,
+                        uint64_t* d_utf8_result, wsg_msg* d_msgs, uint64_t* d_count, wsg_recv_info* d_info,
+                        void* stream)
+{
+    return reply_checked(c, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams, d_state, d_proto, role,
+                         max_message, d_also, reply_op, mask, d_send_key, d_reply, reply_cap, d_reply_off,
+                         d_stream_reply, d_close_off, d_verdict, d_result, d_msgs, d_count, d_info, stream, true, which,
+                         d_valid, d_utf8_result);
 }
 
 int wsg_reply_checked_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_stream_span* d_span,
@@ -437,6 +542,36 @@ int wsg_reply_checked_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_l
                                                      d_send_key, d_reply, reply_cap, d_reply_off, d_stream_reply,
                                                      d_close_off, d_verdict, d_result, d_msgs, d_count, d_info,
                                                      stream);
+                        });
+}
+
+int wsg_reply_validated_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_stream_span* d_span,
+                                uint32_t n_streams, wsg_stream_state* d_state, uint64_t* d_frame_start,
+                                uint32_t frame_cap, uint32_t* d_stream_first, wsg_proto_state* d_proto, uint32_t role,
+                                uint64_t max_message, uint32_t which, const uint8_t reply_op[5], int mask,
+                                const uint32_t* d_send_key, uint8_t* d_reply, uint64_t reply_cap,
+                                uint64_t* d_reply_off, uint64_t* d_stream_reply, uint64_t* d_close_off,
+                                wsg_proto_verdict* d_verdict, uint64_t* d_result, uint64_t* d_valid,
+                                uint64_t* d_utf8_result, wsg_msg* d_msgs, uint64_t* d_count, wsg_recv_info* d_info,
+                                uint32_t* n_frames_out, void* stream)
+{
+    if (!c || !n_frames_out || !d_count || !reply_op || !d_reply_off || !d_stream_reply || !d_close_off || !d_proto ||
+        !d_verdict || !d_result || !d_utf8_result || (n_streams && !d_state) || (reply_cap && !d_reply) ||
+        (frame_cap && (!d_msgs || !d_info || !d_valid)) || !aligned16(d_reply) || role > WSG_PROTO_CLIENT)
+        return WSG_EINVAL;
+    if (c->check &&
+        (!in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) || !in_alloc(d_reply, reply_cap) ||
+         !in_alloc(d_reply_off, (uint64_t(frame_cap) + 1) * 8) ||
+         !in_alloc(d_msgs, uint64_t(frame_cap) * sizeof(wsg_msg)) || !in_alloc(d_valid, uint64_t(frame_cap) * 8) ||
+         !in_alloc(d_info, uint64_t(frame_cap) * sizeof(wsg_recv_info))))
+        return WSG_EINVAL;
+    return streams_then(c, d_wire, wire_len, d_span, n_streams, d_state, d_frame_start, frame_cap, d_stream_first,
+                        d_count, n_frames_out, stream, [&](uint32_t n) {
+                            return wsg_reply_validated(c, d_wire, wire_len, d_frame_start, n, d_stream_first,
+                                                       n_streams, d_state, d_proto, role, max_message, nullptr, which,
+                                                       reply_op, mask, d_send_key, d_reply, reply_cap, d_reply_off,
+                                                       d_stream_reply, d_close_off, d_verdict, d_result, d_valid,
+                                                       d_utf8_result, d_msgs, d_count, d_info, stream);
                         });
 }
 

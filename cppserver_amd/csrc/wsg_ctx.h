@@ -61,6 +61,10 @@ struct wsg_ctx {
                                    // $WSG_DEC_BLOCKS_PER_CU (tests: several tiles per block)
     // k_utf8_scan grid cap (a block takes 4 KiB per pass); $WSG_UTF8_BLOCKS_PER_CU (tests: several passes per block)
     int utf8_blocks_per_cu = 32;
+    // k_utf8_wire grid cap (a wave takes one 4 KiB piece per pass and its loads wait for its record: with every
+    // piece in a wave of its own C2 / ASCII took 50.2 us, at k_utf8_scan's cap 59.6; tools/validbench.py);
+    // $WSG_UTF8_WIRE_BLOCKS_PER_CU (tests: several pieces per wave)
+    int utf8_wire_blocks_per_cu = 128;
     int fan_waves_per_cu = 6;    // fan-out period path: waves per CU (tools/c4_ab.py, graph-replayed C4: 6 -> 8.10 us, 4 -> 8.16, 8 -> 8.32)
     // fan-out period path: waves per workgroup (A/B $WSG_FAN_WPB; one-wave
     // workgroups measured best: C4 8.5 us against 9.3 at 4 and 9.0 at 8-16,

@@ -149,6 +149,7 @@ hipError_t launch_reply_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_l
 // d_result and d_count[0..5) besides launch_reply_plan's outputs.
 // stream_grid: blocks of the per-stream kernels (grid-stride).
 struct ProtoPlan;
+struct Utf8Inside;   // below, with the UTF-8 launchers
 hipError_t launch_reply_checked_plan(hipStream_t s, int stream_grid, const uint8_t* wire, uint64_t wire_len,
                                      const uint64_t* fs, uint32_t n, const uint32_t* stream_first, uint32_t n_streams,
                                      wsg_stream_state* state, wsg_proto_state* proto, uint32_t role,
@@ -157,7 +158,8 @@ hipError_t launch_reply_checked_plan(hipStream_t s, int stream_grid, const uint8
                                      uint64_t* stream_reply, uint64_t* close_off, wsg_proto_verdict* verdict,
                                      uint64_t* result, wsg_msg* msgs, uint64_t* count, wsg_recv_info* info,
                                      const MsgPlan& plan, const ProtoPlan& pplan, MsgPiece* pieces,
-                                     uint64_t pieces_cap, unsigned long long* err);
+                                     uint64_t pieces_cap, unsigned long long* err,
+                                     const Utf8Inside* utf8 = nullptr);
 // k_msg_gather over those records: every replied payload byte, re-keyed, to its place in reply.
 hipError_t launch_reply_gather(hipStream_t s, int grid, const uint8_t* wire, const MsgPlan& plan,
                                const MsgPiece* pieces, uint64_t pieces_cap, uint8_t* reply, uint64_t reply_cap);
@@ -207,6 +209,40 @@ hipError_t launch_utf8_count(hipStream_t s, int grid, const wsg_msg* msgs, const
 hipError_t launch_utf8_verdicts(hipStream_t s, int rec_grid, int stream_grid, const wsg_msg* msgs,
                                 const uint64_t* count, uint32_t msg_room, uint32_t which, const uint64_t* valid,
                                 uint32_t n_streams, wsg_proto_verdict* also);
+
+// ---- UTF-8 from the masked wire (wsg_check_utf8_wire; wsg_utf8.hip) ---------
+// The payload kernel over the message plan's piece records (launch_msg_plan's,
+// read as 4 KiB pieces of the wire), one wave per record, grid-stride: every
+// payload byte of a delivered frame loaded once and unmasked in registers;
+// d_valid as launch_utf8_scan leaves it for the dense layout of the same
+// messages.  Between launch_utf8_init and launch_utf8_count (msg_cap
+// UINT64_MAX: every record lies inside the layout).
+hipError_t launch_utf8_wire(hipStream_t s, int grid, const uint8_t* wire, uint64_t wire_len, const MsgPlan& plan,
+                            const MsgPiece* pieces, uint64_t pieces_cap, const wsg_msg* msgs, const uint64_t* count,
+                            uint32_t msg_room, uint32_t which, uint64_t* valid);
+// wsg_reply_validated: launch_utf8_verdicts over a seed that is also_in[j]
+// (null: none) where that names a frame of stream j, all 0xFF otherwise.
+hipError_t launch_utf8_verdicts_over(hipStream_t s, int rec_grid, int stream_grid, uint32_t n,
+                                     const uint32_t* stream_first, const wsg_proto_verdict* also_in,
+                                     const wsg_msg* msgs, const uint64_t* count, uint32_t msg_room, uint32_t which,
+                                     const uint64_t* valid, uint32_t n_streams, uint64_t* also);
+// wsg_check_utf8_wire's plan pass: launch_msg_plan with no capacity and
+// without k_msg_state, so d_state is read (the sticky-opcode seed) and not written.
+hipError_t launch_msg_plan_only(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
+                                const uint32_t* stream_first, uint32_t n_streams, const wsg_stream_state* state,
+                                wsg_msg* msgs, uint64_t* count, wsg_recv_info* info, const MsgPlan& plan,
+                                MsgPiece* pieces, uint64_t pieces_cap, unsigned long long* err);
+// What wsg_reply_validated adds to launch_reply_checked_plan: the UTF-8 check
+// from the wire between the protocol judge and the merge, on the dense piece
+// records of k_msg_finalize, and its verdicts merged with the caller's.
+struct Utf8Inside {
+    uint32_t which;
+    uint64_t* valid;     // n words
+    uint64_t* result;    // 4 words
+    uint64_t* also;      // n_streams words of scratch: the merged d_also
+    int rec_grid;        // blocks of the per-record kernels (at least one)
+    int wire_grid;       // blocks of k_utf8_wire
+};
 
 // ---- protocol rules on the device (wsg_check_protocol; wsg_proto.hip) -------
 struct ProtoStep;   // wsg_proto.h

@@ -702,7 +702,7 @@ template <class Finish>
 static hipError_t launch_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
                               const uint32_t* stream_first, uint32_t n_streams, wsg_stream_state* state,
                               uint64_t msg_cap, uint64_t* count, uint32_t count_words, wsg_recv_info* info,
-                              const MsgPlan& plan, unsigned long long* err, Finish finish)
+                              const MsgPlan& plan, unsigned long long* err, Finish finish, bool write_state = true)
 {
     const uint32_t nb = uint32_t((uint64_t(n) + BLOCK - 1) / BLOCK);
     if (n == 0) {
@@ -717,7 +717,7 @@ static hipError_t launch_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_
         k_msg_bytes_blocks<<<1, BLOCK, 0, s>>>(plan, nb, n, msg_cap, count, err);
         finish(nb);
     }
-    if (n_streams)
+    if (n_streams && write_state)
         k_msg_state<<<(n_streams + BLOCK - 1) / BLOCK, BLOCK, 0, s>>>(info, n, stream_first, n_streams, state, plan);
     return hipGetLastError();
 }
@@ -732,6 +732,20 @@ hipError_t launch_msg_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_len
                            k_msg_finalize<<<nb, BLOCK, 0, s>>>(wire, info, n, stream_first, state, plan, msgs, pieces,
                                                                pieces_cap);
                        });
+}
+
+// (d_state is only read: k_msg_finalize takes the opcode seed from it, k_msg_state is left out)
+hipError_t launch_msg_plan_only(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
+                                const uint32_t* stream_first, uint32_t n_streams, const wsg_stream_state* state,
+                                wsg_msg* msgs, uint64_t* count, wsg_recv_info* info, const MsgPlan& plan,
+                                MsgPiece* pieces, uint64_t pieces_cap, unsigned long long* err)
+{
+    return launch_plan(
+        s, wire, wire_len, fs, n, stream_first, n_streams, nullptr, UINT64_MAX, count, 2, info, plan, err,
+        [&](uint32_t nb) {
+            k_msg_finalize<<<nb, BLOCK, 0, s>>>(wire, info, n, stream_first, state, plan, msgs, pieces, pieces_cap);
+        },
+        false);
 }
 
 hipError_t launch_msg_gather(hipStream_t s, int grid, const uint8_t* wire, const MsgPlan& plan,
@@ -778,7 +792,7 @@ hipError_t launch_reply_checked_plan(hipStream_t s, int stream_grid, const uint8
                                      uint64_t* stream_reply, uint64_t* close_off, wsg_proto_verdict* verdict,
                                      uint64_t* result, wsg_msg* msgs, uint64_t* count, wsg_recv_info* info,
                                      const MsgPlan& plan, const ProtoPlan& pplan, MsgPiece* pieces,
-                                     uint64_t pieces_cap, unsigned long long* err)
+                                     uint64_t pieces_cap, unsigned long long* err, const Utf8Inside* utf8)
 {
     hipError_t pe = hipSuccess;   // of the protocol launchers (each has taken its launch's error)
     const auto keep = [&pe](hipError_t e) {
@@ -799,6 +813,8 @@ hipError_t launch_reply_checked_plan(hipStream_t s, int stream_grid, const uint8
                 return e;
         keep(launch_proto_scan(s, info, n, stream_first, n_streams, proto, pplan, verdict, result));
         keep(launch_proto_finish(s, stream_grid, n, stream_first, n_streams, state, proto, pplan, verdict, result));
+        if (utf8)   // no record: d_utf8_result's seed is its value
+            keep(launch_utf8_init(s, 1, msgs, count, 0, utf8->valid, utf8->result));
     }
     const hipError_t e = launch_plan(
         s, wire, wire_len, fs, n, stream_first, n_streams, state, UINT64_MAX, count, 5, info, plan, err,
@@ -808,6 +824,21 @@ hipError_t launch_reply_checked_plan(hipStream_t s, int stream_grid, const uint8
             keep(launch_proto_scan(s, info, n, stream_first, n_streams, proto, pplan, verdict, result));
             keep(launch_proto_judge(s, wire, wire_len, info, n, stream_first, state, proto, role, max_message, pplan,
                                     verdict));
+            if (utf8) {
+                // wsg_reply_validated: the dense piece records (the reply's replace them below), the
+                // check from the wire over them, its verdicts beside the caller's
+                k_msg_finalize<<<nb, BLOCK, 0, s>>>(wire, info, n, stream_first, state, plan, msgs, pieces,
+                                                    pieces_cap);
+                keep(launch_utf8_init(s, utf8->rec_grid, msgs, count, n, utf8->valid, utf8->result));
+                if (utf8->which)
+                    keep(launch_utf8_wire(s, utf8->wire_grid, wire, wire_len, plan, pieces, pieces_cap, msgs, count,
+                                          n, utf8->which, utf8->valid));
+                keep(launch_utf8_count(s, utf8->rec_grid, msgs, count, n, UINT64_MAX, utf8->which, utf8->valid,
+                                       utf8->result));
+                keep(launch_utf8_verdicts_over(s, utf8->rec_grid, stream_grid, n, stream_first, also, msgs, count, n,
+                                               utf8->which, utf8->valid, n_streams, utf8->also));
+                also = reinterpret_cast<const wsg_proto_verdict*>(utf8->also);
+            }
             if (also)
                 keep(launch_proto_merge(s, stream_grid, n, stream_first, n_streams, also, verdict));
             keep(launch_proto_finish(s, stream_grid, n, stream_first, n_streams, state, proto, pplan, verdict, result));

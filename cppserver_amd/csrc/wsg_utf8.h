@@ -1,5 +1,5 @@
 // wsg_utf8.h — well-formed UTF-8 (RFC 3629) as a position-local rule, shared
-// by the host helper wsg_utf8_valid_up_to and the gfx950 kernel k_utf8_scan
+// by the host helper wsg_utf8_valid_up_to and the gfx950 kernels k_utf8_scan and k_utf8_wire
 // (one source of truth, as wsg_frame.h is for the frame arithmetic).
 //
 // RFC 6455 5.6 / 8.1 want a text message, taken over all its fragments, to be

@@ -1,4 +1,5 @@
-// wsg_utf8.hip — UTF-8 validation of decoded messages (wsg_check_utf8).
+// wsg_utf8.hip — UTF-8 validation of decoded messages (wsg_check_utf8) and of
+// messages read where they lie in the masked wire (wsg_check_utf8_wire).
 #include "wsg_device.h"
 #include "wsg_utf8.h"
 
@@ -132,7 +133,218 @@ __device__ __forceinline__ uint32_t utf8_chunk_bad(uint32_t pre, v4u c, uint32_t
     return bad;
 }
 
+// ---- UTF-8 from the masked wire (wsg_check_utf8_wire) -------------------------
+// The same rule with no d_msg: the message plan's piece records (k_msg_finalize:
+// one frame's payload offset, dense offset, length and key, in dense order) say
+// where every message byte sits in the wire and under which key.  A record's
+// k is read here as the k-th 4 KiB of the WIRE from the 128-byte line of the
+// payload's first byte, which needs no more records than the dense cut the
+// plan counted (poff mod 128 <= 127), leaves at most one record of a frame
+// empty, and makes every chunk of a wave an aligned 16-byte block of d_wire.
+struct WirePiece {
+    uint64_t ws, we;   // its payload bytes: wire [ws, we); ws >= we: none.  Its first row: ws & ~(PIECE_ALIGN - 1)
+    uint64_t delta;    // dense position of wire byte x: x + delta (mod 2^64)
+    uint32_t key;      // the frame's key at wire phase: byte x is masked with key byte x mod 4
+};
+
+__device__ __forceinline__ WirePiece utf8_wire_piece(const MsgPiece* __restrict__ rec, uint64_t wire_len)
+{
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(rec);
+    const uint64_t poff = uint64_t(w[0]) | (uint64_t(w[1]) << 32);
+    const uint64_t d0 = uint64_t(w[2]) | (uint64_t(w[3]) << 32);
+    const uint64_t len = uint64_t(w[4]) | (uint64_t(w[5]) << 32);
+    const uint64_t lo = (poff & ~(PIECE_ALIGN - 1)) + uint64_t(w[7]) * PIECE;
+    const uint64_t end = poff + len;
+    WirePiece p;
+    p.delta = d0 - poff;
+    p.key = key_rot(w[6], 0u - uint32_t(poff));   // payload byte i lies at wire offset poff + i
+    p.ws = max(lo, poff);
+    p.we = min(lo + PIECE, end);
+    if (end < poff || end > wire_len)   // (not a frame of this wire: never a read outside it)
+        p.ws = p.we = 0;
+    return p;
+}
+
+// The up-to-3 message bytes in front of piece q's first byte, unmasked, as the
+// dword of the positions -4..-1 (00 where there is none): they lie in the
+// records before q, one frame and key each, however many empty, failed or
+// control frames the wire holds between them.  A frame has at most one empty
+// record and every other record holds a byte, so six records always suffice.
+__device__ __forceinline__ uint32_t utf8_wire_before(const uint8_t* __restrict__ wire, uint64_t wire_len,
+                                                     const MsgPiece* __restrict__ recs, uint64_t q)
+{
+    uint32_t h = 0, got = 0;
+    for (uint32_t step = 0; step < 8 && q > 0 && got < 3; ++step) {
+        const WirePiece P = utf8_wire_piece(recs + --q, wire_len);
+        for (uint64_t p = P.we; p > P.ws && got < 3; ++got) {
+            --p;
+            h |= (uint32_t(wire[p]) ^ key_byte(P.key, p)) << (8u * (3u - got));
+        }
+    }
+    return h;
+}
+
+// ... and behind its last byte: the dword of the positions 0..3 from there.
+__device__ __forceinline__ uint32_t utf8_wire_after(const uint8_t* __restrict__ wire, uint64_t wire_len,
+                                                    const MsgPiece* __restrict__ recs, uint64_t q, uint64_t pieces)
+{
+    uint32_t t = 0, got = 0;
+    for (uint32_t step = 0; step < 8 && q + 1 < pieces && got < 3; ++step) {
+        const WirePiece P = utf8_wire_piece(recs + ++q, wire_len);
+        for (uint64_t p = P.ws; p < P.we && got < 3; ++p, ++got)
+            t |= (uint32_t(wire[p]) ^ key_byte(P.key, p)) << (8u * got);
+    }
+    return t;
+}
+
+// d[0..6) is the window -4..19 of a chunk; h holds 4 bytes for the window
+// indices [wi, wi + 4) (wi in (-4, 24); the window is 00 where h has a byte).
+__device__ __forceinline__ void utf8_window_or(uint32_t d[6], int wi, uint32_t h)
+{
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const int s = wi - 4 * k;
+        if (s > -4 && s < 4)
+            d[k] |= s >= 0 ? h << (8 * s) : h >> (8 * -s);
+    }
+}
+
+// Bit i: byte i of the chunk is >= 0x80.  (Bit 7 of a dword's four bytes
+// gathered by one multiplication: the sixteen partial products meet nowhere.)
+__device__ __forceinline__ uint32_t utf8_chunk_high(v4u c)
+{
+    uint32_t bits = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        bits |= ((((c[k] >> 7) & 0x01010101u) * 0x01020408u) >> 24 & 0xFu) << (4 * k);
+    return bits;
+}
+
+// Row u (wave-uniform, run time) of a piece's chunks, by selects: the rows stay in registers.
+__device__ __forceinline__ v4u utf8_row(const v4u (&c)[EU], uint32_t u)
+{
+    v4u r = c[0];
+#pragma unroll
+    for (int k = 1; k < EU; ++k)
+        r = u == uint32_t(k) ? c[k] : r;
+    return r;
+}
+
+// Bits [x, 16) of a chunk's 16 positions.
+__device__ __forceinline__ uint32_t utf8_bits_from(int64_t x)
+{
+    return x <= 0 ? 0xFFFFu : x >= 16 ? 0u : (0xFFFFu << uint32_t(x)) & 0xFFFFu;
+}
+
 } // namespace
+
+// One wave per piece record (grid-stride), EU rows of 64 aligned 16-byte
+// chunks: one nontemporal load each, XOR with the key at the chunk's payload
+// phase (wave-uniform: chunks are 16 apart), the bytes outside the piece's
+// payload cleared in the two chunks that hold its ends.  No byte >= 0x80 in
+// the wave: done.  Otherwise one search of d_msgs finds the one message the
+// piece's frame belongs to (a close message's checked range starts 2 bytes
+// into its buffer: the window's bounds see to that); a piece of an unselected
+// message is done.  The 4 bytes either side of a chunk come from the
+// neighbouring lanes' and rows' registers, and the 3 on either side of the
+// piece from the neighbouring records, fetched only where the message goes on
+// beyond the piece and a byte >= 0x80 lies within 3 bytes of that end.  Only
+// the piece's own positions are judged.
+__global__ __launch_bounds__(BLOCK) void k_utf8_wire(const uint8_t* __restrict__ wire, uint64_t wire_len,
+                                                     const uint64_t* __restrict__ tot,
+                                                     const MsgPiece* __restrict__ piece_recs, uint64_t pieces_cap,
+                                                     const wsg_msg* __restrict__ msgs,
+                                                     const uint64_t* __restrict__ count, uint32_t msg_room,
+                                                     uint32_t which, unsigned long long* __restrict__ valid)
+{
+    const uint32_t M = uint32_t(min(count[0], uint64_t(msg_room)));
+    if (M == 0)
+        return;
+    const uint32_t waves = gridDim.x * (BLOCK / 64);
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t pieces = uint32_t(min(min(tot[3], pieces_cap), uint64_t(UINT32_MAX)));   // (the host's bound fits a word)
+    // (wave-uniform loop: every lane of a wave takes part in the shuffles)
+    for (uint64_t q = uint64_t(blockIdx.x) * (BLOCK / 64) + wave_id(); q < pieces; q += waves) {
+        const WirePiece P = utf8_wire_piece(piece_recs + q, wire_len);
+        if (P.ws >= P.we)
+            continue;   // piece counts are an upper bound
+        const uint64_t row0 = P.ws & ~(PIECE_ALIGN - 1);
+        const uint32_t kw = P.key;   // (every chunk starts at a wire offset that is 0 mod 4)
+        v4u c[EU];
+#pragma unroll
+        for (int u = 0; u < EU; ++u) {
+            const uint64_t a = row0 + (uint64_t(u) * 64 + lane) * CHUNK;
+            c[u] = a < P.we && a + CHUNK > P.ws ? ld16nt(wire + a) : v4u{0, 0, 0, 0};
+        }
+        uint32_t hot = 0;
+#pragma unroll
+        for (int u = 0; u < EU; ++u) {
+            const uint64_t a = row0 + (uint64_t(u) * 64 + lane) * CHUNK;
+            const bool in = a < P.we && a + CHUNK > P.ws;
+            c[u] = in ? c[u] ^ kw : c[u];
+            if (in && (a < P.ws || a + CHUNK > P.we)) {   // a chunk shared with the header or the next frame
+                const int lo = a < P.ws ? int(P.ws - a) : 0, hi = P.we - a < CHUNK ? int(P.we - a) : int(CHUNK);
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    c[u][k] &= low_bytes(hi - 4 * k) & ~low_bytes(lo - 4 * k);
+            }
+            hot |= uint32_t(((c[u].x | c[u].y | c[u].z | c[u].w) & UTF8_H) != 0) << u;   // a bad position is never an ASCII byte
+        }
+        if (__ballot(hot != 0) == 0)
+            continue;
+        const uint64_t dlo = P.ws + P.delta, dhi = P.we + P.delta;   // the piece in the dense layout
+        const uint32_t m = uni(utf8_first_beyond_wave(msgs, 0, M, dlo));
+        if (m >= M)
+            continue;
+        const Utf8Rec r = utf8_rec(msgs, m, which);
+        if (!r.selected)
+            continue;
+        // a byte >= 0x80 among the piece's first / last 3 bytes, with message bytes beyond that end
+        uint32_t near_head = 0, near_tail = 0;
+#pragma unroll
+        for (int u = 0; u < EU; ++u) {
+            const uint64_t a = row0 + (uint64_t(u) * 64 + lane) * CHUNK;
+            const int64_t wh = int64_t(P.ws - a), wt = int64_t(P.we - a);
+            const uint32_t bytes = utf8_chunk_high(c[u]);
+            near_head |= bytes & utf8_bits_from(wh) & ~utf8_bits_from(wh + 3);
+            near_tail |= bytes & utf8_bits_from(wt - 3) & ~utf8_bits_from(wt);
+        }
+        uint32_t head = 0, tail = 0;
+        if (dlo > r.off && __ballot(near_head != 0) != 0)
+            head = utf8_wire_before(wire, wire_len, piece_recs, q);
+        if (dhi < r.end && __ballot(near_tail != 0) != 0)
+            tail = utf8_wire_after(wire, wire_len, piece_recs, q, pieces);
+        // (one copy of the rule's code: the row in hand picked out of the registers by selects)
+#pragma unroll 1
+        for (uint32_t u = 0; u < uint32_t(EU); ++u) {
+            if (__ballot((hot >> u) & 1u) == 0)
+                continue;
+            const v4u cu = utf8_row(c, u);
+            uint32_t pre = uint32_t(__shfl_up(cu.w, 1, 64)), post = uint32_t(__shfl_down(cu.x, 1, 64));
+            const uint32_t row_before = u ? uint32_t(__builtin_amdgcn_readlane(utf8_row(c, u - 1).w, 63)) : 0u;
+            const uint32_t row_after = u + 1 < uint32_t(EU) ? uint32_t(__builtin_amdgcn_readlane(utf8_row(c, u + 1).x, 0)) : 0u;
+            pre = lane == 0 ? row_before : pre;
+            post = lane == 63 ? row_after : post;
+            if (!((hot >> u) & 1u))
+                continue;
+            const uint64_t a = row0 + (uint64_t(u) * 64 + lane) * CHUNK;
+            const int64_t wh = int64_t(P.ws - a), wt = int64_t(P.we - a);   // the piece's ends, from the chunk
+            uint32_t d[6] = {pre, cu.x, cu.y, cu.z, cu.w, post};
+            if (head && wh > -4 && wh < 24)
+                utf8_window_or(d, int(wh), head);            // positions ws - 4 .. ws - 1
+            if (tail && wt > -8 && wt < 20)
+                utf8_window_or(d, int(wt) + 4, tail);        // positions we .. we + 3
+            const uint64_t pd = a + P.delta;   // dense position of the chunk's byte 0 (mod 2^64 in front of the payload)
+            const int64_t ro = int64_t(r.off - pd), re = int64_t(r.end - pd);
+            const int lo = ro < -4 ? -4 : ro > 20 ? 20 : int(ro), hi = re < -4 ? -4 : re > 20 ? 20 : int(re);
+            // (only the piece's own positions: the context bytes are judged by their own waves)
+            const uint32_t bad = utf8_chunk_bad(d[0], v4u{d[1], d[2], d[3], d[4]}, d[5], lo, hi) & utf8_bits_from(wh) &
+                                 ~utf8_bits_from(wt);
+            if (bad)
+                atomicMin(valid + m, static_cast<unsigned long long>(pd + uint32_t(__builtin_ctz(bad)) - r.off));
+        }
+    }
+}
 
 // One lane per record (grid-stride): d_valid[m] = len; the first lane seeds
 // d_result = {0, UINT64_MAX, 0, 0} for k_utf8_count behind it.  (A kernel's
@@ -285,6 +497,46 @@ hipError_t launch_utf8_verdicts(hipStream_t s, int rec_grid, int stream_grid, co
     k_utf8_verdict_seed<<<stream_grid, BLOCK, 0, s>>>(n_streams, a);
     if (msg_room && n_streams)
         k_utf8_verdicts<<<rec_grid, BLOCK, 0, s>>>(msgs, count, msg_room, which, valid, n_streams, a);
+    return hipGetLastError();
+}
+
+// wsg_reply_validated: the seed of its verdict scratch, one lane per stream:
+// the caller's d_also[j] where it is given, is not all 0xFF and names a frame
+// of stream j, all 0xFF otherwise, so that an entry k_proto_merge would
+// ignore never stands below a UTF-8 verdict in k_utf8_verdicts' minimum.
+__global__ __launch_bounds__(BLOCK) void k_utf8_also_seed(uint32_t n, const uint32_t* __restrict__ sf, uint32_t ns,
+                                                          const uint64_t* __restrict__ also_in,
+                                                          unsigned long long* __restrict__ also)
+{
+    for (uint64_t j = uint64_t(blockIdx.x) * BLOCK + threadIdx.x; j < ns; j += uint64_t(gridDim.x) * BLOCK) {
+        uint64_t a = also_in ? also_in[j] : UINT64_MAX;
+        const uint32_t frame = uint32_t(a >> 32);
+        const uint32_t start = min(sf[j], n), end = max(min(sf[j + 1], n), start);
+        if (frame < start || frame >= end)
+            a = UINT64_MAX;
+        also[j] = a;
+    }
+}
+
+hipError_t launch_utf8_verdicts_over(hipStream_t s, int rec_grid, int stream_grid, uint32_t n,
+                                     const uint32_t* stream_first, const wsg_proto_verdict* also_in,
+                                     const wsg_msg* msgs, const uint64_t* count, uint32_t msg_room, uint32_t which,
+                                     const uint64_t* valid, uint32_t n_streams, uint64_t* also)
+{
+    unsigned long long* a = reinterpret_cast<unsigned long long*>(also);
+    k_utf8_also_seed<<<stream_grid, BLOCK, 0, s>>>(n, stream_first, n_streams,
+                                                   reinterpret_cast<const uint64_t*>(also_in), a);
+    if (msg_room && n_streams && which)
+        k_utf8_verdicts<<<rec_grid, BLOCK, 0, s>>>(msgs, count, msg_room, which, valid, n_streams, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_utf8_wire(hipStream_t s, int grid, const uint8_t* wire, uint64_t wire_len, const MsgPlan& plan,
+                            const MsgPiece* pieces, uint64_t pieces_cap, const wsg_msg* msgs, const uint64_t* count,
+                            uint32_t msg_room, uint32_t which, uint64_t* valid)
+{
+    k_utf8_wire<<<grid, BLOCK, 0, s>>>(wire, wire_len, plan.tot, pieces, pieces_cap, msgs, count, msg_room, which,
+                                       reinterpret_cast<unsigned long long*>(valid));
     return hipGetLastError();
 }
 

@@ -333,6 +333,26 @@ def utf8_plan(msgs, msg_bytes, which, msg_cap=None):
     return valid, np.array([invalid, lowest, checked, nbytes], dtype=np.uint64)
 
 
+def utf8_wire_plan(info, stream_first, state, payload, which):
+    """wsg_check_utf8_wire restated on the host: message_plan over the frame
+    table, the dense message bytes gathered from ``payload`` (the batch with
+    its payloads unmasked where they sit, wsg_decode_batch's output) and
+    utf8_plan over them.  Returns (msgs, count, valid, result); ``state`` is
+    only read."""
+    info = np.asarray(info, dtype=RECV_INFO)
+    msgs, count, new_state = message_plan(info, stream_first, state, payload)
+    sf = np.asarray(stream_first, dtype=np.int64)
+    buf = np.asarray(payload, dtype=np.uint8)
+    dense = []
+    for j in range(len(sf) - 1):   # the delivered frames: every stream's consumed ones, in order
+        for i in range(int(sf[j]), int(sf[j]) + int(new_state["consumed"][j])):
+            dense.append(buf[int(info["payload_off"][i]): int(info["payload_off"][i]) + int(info["len"][i])])
+    dense = np.concatenate(dense) if dense else np.zeros(0, dtype=np.uint8)
+    assert len(dense) == int(count[1])
+    valid, result = utf8_plan(msgs, dense, which)
+    return msgs, count, valid, result
+
+
 # wsg_check_protocol (include/wsg_capi.h): the per-stream state, the verdict
 # and the WSG_PV_* / WSG_PROTO_* constants.
 PROTO_STATE = np.dtype([("bytes", "<u8"), ("open", "u1"), ("_pad", "u1", (7,))])
@@ -501,6 +521,24 @@ def utf8_verdicts(msgs, valid, which, n_streams):
     fin = msgs["first_frame"].astype(np.uint64) + msgs["nframes"].astype(np.uint64) - np.uint64(1)
     word = np.uint64(PV_UTF8) | (np.uint64(1007) << np.uint64(16)) | (fin << np.uint64(32))
     np.minimum.at(words, msgs["stream"][bad].astype(np.int64), word[bad])
+    return words.view(PROTO_VERDICT)
+
+
+def validated_verdicts(msgs, valid, which, also, stream_first):
+    """The d_also that wsg_reply_validated hands to its reply kernels: per
+    stream the UTF-8 verdict (utf8_verdicts), the caller's ``also`` entry
+    (None: none) where that is not all 0xFF and names a frame of the stream,
+    or the lower of the two as one little-endian word.  An entry outside its
+    stream's range is dropped before the comparison."""
+    sf = np.asarray(stream_first, dtype=np.int64)
+    n_streams = len(sf) - 1
+    words = _verdict_words(utf8_verdicts(msgs, valid, which, n_streams)) if n_streams else np.zeros(0, dtype="<u8")
+    if also is not None:
+        given = np.asarray(also, dtype=PROTO_VERDICT)
+        a = _verdict_words(given)
+        for j in range(n_streams):
+            if int(a[j]) != U64_MAX and int(sf[j]) <= int(given["frame"][j]) < int(sf[j + 1]):
+                words[j] = min(int(words[j]), int(a[j]))
     return words.view(PROTO_VERDICT)
 
 

@@ -24,8 +24,9 @@
  * block, piece records) and wsg_frame_streams calls a third (per-stream frame
  * counts, scan partials; wsg_decode_streams and wsg_reply_streams are one
  * call of each of the last two) and wsg_check_protocol calls a fourth (the
- * frames' streams, scan partials, per-stream states; wsg_reply_checked uses
- * the second and the fourth and is ordered with the users of both);
+ * frames' streams, scan partials, per-stream states; wsg_reply_checked and
+ * wsg_reply_validated use the second and the fourth and are ordered with the
+ * users of both; wsg_check_utf8_wire uses the second);
  * wsg_decode_batch, wsg_check_utf8, wsg_utf8_verdicts and the fan-out calls use none.  The calls that
  * share a scratch are ordered across streams on the device, in the order they
  * were made: a call on another stream than the previous one first waits
@@ -386,6 +387,54 @@ int wsg_check_utf8(wsg_ctx* ctx, const uint8_t* d_msg, uint64_t msg_cap,
                    const wsg_msg* d_msgs, const uint64_t* d_count, uint32_t msg_room,
                    uint32_t which, uint64_t* d_valid, uint64_t* d_result, void* stream);
 
+/* ---- UTF-8 checked from the masked wire: no d_msg --------------------------- */
+/* (Added without an ABI bump: symbols only.)
+ *
+ * wsg_check_utf8 over the messages of a frame table, read where they lie in
+ * d_wire: masked, cut into fragments, with other frames between them.  The
+ * call runs the message plan of wsg_decode_messages itself and unmasks in
+ * registers; there is no dense message buffer.
+ *
+ * Inputs.  d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams as
+ * wsg_decode_messages takes them.  d_state is read and NOT written: each
+ * stream's sticky opcode is the seed, and a reply call behind this one sees
+ * the same seed.  `which`: the WSG_UTF8_* bits.
+ * Outputs of the plan.  d_info, d_msgs, d_count[0..1] and the frame-error
+ * latch are exactly what wsg_decode_messages writes for the same arguments
+ * (with a msg_cap that holds everything: WSG_ENOMEM is never latched);
+ * d_msgs[m].off / len describe the dense layout, although no such buffer
+ * exists.
+ * UTF-8 outputs.  d_valid[0..d_count[0]) (room for n words) and
+ * d_result[0..4) are exactly what wsg_check_utf8 writes for that dense layout
+ * with msg_room = n and a msg_cap that holds everything: the same selection
+ * by `which` from kind and opcode, valid_up_to over the message's callback
+ * data, every byte outside [off, off + len) counting as 00 (a close message's
+ * two status bytes and the neighbouring message's bytes too), d_valid[m] of
+ * an unselected message its len, d_result = {invalid, lowest, checked,
+ * bytes}.  Deterministic.
+ * Bytes read.  Every payload byte of a delivered frame is loaded once, as
+ * part of its aligned 16-byte block; beside that only the up-to-3 message
+ * bytes either side of a 4 KiB piece of a frame, where a sequence can cross
+ * that edge.  No byte of d_wire at or past the end of its last 16-byte block
+ * is read, and bytes at or past wire_len never influence a result.  A frame
+ * with an error contributes no bytes, as in the plan.
+ * Asynchronous on `stream`.  Nothing but frame errors is latched: invalid
+ * text is a result.  The call uses the message plan's scratch of the ctx, so
+ * it enters and leaves that order (see "Streams" above), with the usual
+ * capture rule: run it once uncaptured with the same n and wire_len first.
+ * n == 0, n_streams == 0, which == 0 and empty streams are valid.  WSG_EINVAL
+ * for a NULL operand (d_wire when wire_len, the tables when n, d_state when
+ * n_streams, d_count, d_result, d_stream_first), d_wire not 16-byte aligned,
+ * any other operand not 8-byte aligned (4 for d_stream_first), and under
+ * WSG_CHECK=1 for an operand too short for its allocation.  The timing hook
+ * brackets the payload kernel.                                               */
+int wsg_check_utf8_wire(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
+                        const uint64_t* d_frame_start, uint32_t n,
+                        const uint32_t* d_stream_first, uint32_t n_streams,
+                        const wsg_stream_state* d_state, uint32_t which,
+                        wsg_msg* d_msgs, uint64_t* d_count /* 2 words */, wsg_recv_info* d_info,
+                        uint64_t* d_valid /* n words */, uint64_t* d_result /* 4 words */, void* stream);
+
 /* Length of the longest well-formed UTF-8 prefix of buf[0..len) (RFC 3629);
  * len when the whole buffer is valid.  Host; the rule the kernel runs. */
 uint64_t wsg_utf8_valid_up_to(const uint8_t* buf, uint64_t len);
@@ -606,10 +655,68 @@ int wsg_reply_checked_streams(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire
  * wsg_decode_messages -> wsg_check_utf8 -> wsg_utf8_verdicts ->
  * wsg_reply_checked(d_also), all on one stream with no synchronisation.  Its
  * cost: the payload is moved twice, once into d_msg for the check and once
- * into the reply (validating straight from the masked wire is not done).     */
+ * into the reply, and the plan runs twice; wsg_reply_validated below is the
+ * same server in one call that validates straight from the masked wire.      */
 int wsg_utf8_verdicts(wsg_ctx* ctx, const wsg_msg* d_msgs, const uint64_t* d_count, uint32_t msg_room,
                       uint32_t which, const uint64_t* d_valid, uint32_t n_streams,
                       wsg_proto_verdict* d_also, void* stream);
+
+/* ---- validated replies: the conformant echo in one call -------------------- */
+/* (Added without an ABI bump: symbols only.)
+ *
+ * wsg_reply_checked with the UTF-8 check inside it.  Every output equals what
+ * this chain writes on one stream:
+ *   wsg_check_utf8_wire(which) -> wsg_utf8_verdicts(which) -> wsg_reply_checked(d_also')
+ * where d_also'[j] is the UTF-8 verdict of stream j, or the caller's d_also[j]
+ * when d_also is given, the entry is not all 0xFF and names a frame inside
+ * stream j's range, or, when both exist, the lower of the two as one
+ * little-endian word.  A caller entry outside its stream's range is dropped
+ * before that comparison: it never shadows a UTF-8 verdict.  The plan runs
+ * once, the payload is read once for the check and once for the reply and
+ * written once; no d_msg exists.
+ * Arguments: those of wsg_reply_checked, `which` (WSG_UTF8_* bits) behind
+ * d_also, and d_valid (n words) and d_utf8_result (4 words) behind d_result,
+ * written as wsg_check_utf8_wire writes them; they are final also when the
+ * replies latch WSG_ENOMEM.  d_verdict / d_result count the effective
+ * verdicts as in wsg_reply_checked: a stream failed for its text shows
+ * {WSG_PV_UTF8, 1007, the FIN frame of its first invalid message} and gets
+ * the 1007 close frame there, unless the protocol or the caller fails it at
+ * an earlier frame.  which == 0 is wsg_reply_checked, byte for byte.
+ * WSG_EINVAL as wsg_reply_checked, and for d_utf8_result NULL, d_valid NULL
+ * with n > 0, or either not 8-byte aligned.  Streams: as wsg_reply_checked
+ * (both scratches of the ctx; the merged verdicts live in the protocol
+ * plan's); the timing hook brackets the reply gather.                        */
+int wsg_reply_validated(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
+                        const uint64_t* d_frame_start, uint32_t n,
+                        const uint32_t* d_stream_first, uint32_t n_streams,
+                        wsg_stream_state* d_state,
+                        wsg_proto_state* d_proto, uint32_t role, uint64_t max_message,
+                        const wsg_proto_verdict* d_also /* or NULL */, uint32_t which,
+                        const uint8_t reply_op[5], int mask, const uint32_t* d_send_key,
+                        uint8_t* d_reply, uint64_t reply_cap,
+                        uint64_t* d_reply_off, uint64_t* d_stream_reply, uint64_t* d_close_off,
+                        wsg_proto_verdict* d_verdict, uint64_t* d_result,
+                        uint64_t* d_valid /* n words */, uint64_t* d_utf8_result /* 4 words */,
+                        wsg_msg* d_msgs, uint64_t* d_count /* 5 words */,
+                        wsg_recv_info* d_info, void* stream);
+
+/* Raw bytes to validated replies: wsg_reply_checked_streams with
+ * wsg_reply_validated (d_also NULL) in the place of wsg_reply_checked; the
+ * same returns, the same lowering of d_span[j].consumed and the same refusal
+ * while capturing; d_valid has room for frame_cap words.  An RFC 6455
+ * conformant echo server's loop is this call and one wsg_sync.               */
+int wsg_reply_validated_streams(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
+                                wsg_stream_span* d_span, uint32_t n_streams, wsg_stream_state* d_state,
+                                uint64_t* d_frame_start, uint32_t frame_cap, uint32_t* d_stream_first,
+                                wsg_proto_state* d_proto, uint32_t role, uint64_t max_message,
+                                uint32_t which,
+                                const uint8_t reply_op[5], int mask, const uint32_t* d_send_key,
+                                uint8_t* d_reply, uint64_t reply_cap,
+                                uint64_t* d_reply_off, uint64_t* d_stream_reply, uint64_t* d_close_off,
+                                wsg_proto_verdict* d_verdict, uint64_t* d_result,
+                                uint64_t* d_valid, uint64_t* d_utf8_result,
+                                wsg_msg* d_msgs, uint64_t* d_count, wsg_recv_info* d_info,
+                                uint32_t* n_frames_out, void* stream);
 
 /* ---- batch encode: header pack + mask (PrepareSendFrame over many frames) */
 /* Frames are written back to back into d_wire (16-byte aligned, capacity

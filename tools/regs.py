@@ -1,8 +1,8 @@
 """Register/occupancy report for k_decode and source variants with paths cut
 out (which path sets the kernel's VGPR count), and for k_msg_gather
 (wsg_decode_messages; wsg_reply_messages runs it too), the reply plan, the
-framer, the UTF-8 check, the protocol check and the checked reply
-(wsg_reply_checked).  Compiles for gfx950 only (no GPU needed).
+framer, the UTF-8 check (dense and from the wire), the protocol check and
+the checked reply (wsg_reply_checked).  Compiles for gfx950 only (no GPU needed).
 
 usage: python tools/regs.py
 """
@@ -58,7 +58,8 @@ if __name__ == "__main__":
                                                 "k_reply_finalize<0>", "k_msg_consumed", "k_reply_local<1>",
                                                 "k_reply_blocks<1>", "k_reply_finalize<1>")),
                           ("wsg_frames.hip", ("k_frame_count", "k_frame_write")),
-                          ("wsg_utf8.hip", ("k_utf8_init", "k_utf8_scan", "k_utf8_count", "k_utf8_verdict_seed", "k_utf8_verdicts")),
+                          ("wsg_utf8.hip", ("k_utf8_init", "k_utf8_scan", "k_utf8_count", "k_utf8_verdict_seed", "k_utf8_verdicts",
+                                            "k_utf8_wire", "k_utf8_also_seed")),
                           ("wsg_proto.hip", ("k_proto_local", "k_proto_blocks", "k_proto_judge", "k_proto_finish",
                                              "k_proto_merge"))):
         src = source(name)
