@@ -21,6 +21,7 @@ from .layout import (  # noqa: F401  (re-exported)
     PROTO_ANY, PROTO_CLIENT, PROTO_SERVER, PROTO_STATE, PROTO_VERDICT, PV_CLOSE_CODE, PV_CLOSE_LEN, PV_CLOSED, PV_CONT,
     PV_CTRL_FRAGMENT, PV_CTRL_LONG, PV_DATA, PV_FRAME, PV_MASK, PV_NONE, PV_OPCODE, PV_RSV, PV_TOO_BIG, protocol_plan,
     PV_UTF8, checked_reply_plan, merge_verdicts, utf8_verdicts, utf8_wire_plan, validated_verdicts,
+    AHEAD_CAP, ASSEMBLY_REFERENCE, ASSEMBLY_RFC, message_frames,
 )
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -64,6 +65,8 @@ def lib(path=None):
         "wsg_destroy": (ci, [vp]),
         "wsg_sync": (ci, [vp, vp]),
         "wsg_stream": (vp, [vp]),
+        "wsg_set_assembly": (ci, [vp, ci]),
+        "wsg_get_assembly": (ci, [vp]),
         "wsg_decode_batch": (ci, [vp, vp, u64, vp, u32, vp, vp, vp]),
         "wsg_decode_messages": (ci, [vp, vp, u64, vp, u32, vp, u32, vp, vp, u64, vp, vp, vp, vp]),
         "wsg_frame_streams": (ci, [vp, vp, u64, vp, u32, vp, u32, vp, vp, vp]),
@@ -139,7 +142,7 @@ def lib(path=None):
         "wsg_lane_events": (ci, [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
     }
     for name, (res, args) in sig.items():
-        if path is not None and not hasattr(L, name):
+        if (path is not None or os.environ.get("WSG_LIB_PATH")) and not hasattr(L, name):
             continue   # an older A/B build of the library (tools/): bind what it has
         fn = getattr(L, name)
         fn.restype = res
@@ -276,6 +279,19 @@ class Codec:
 
     def sync_status(self, stream=None):
         return self._L.wsg_sync(self._ctx, self._stream(stream))
+
+    # -- the assembly rule ---------------------------------------------------
+    def set_assembly(self, mode):
+        """wsg_set_assembly: ASSEMBLY_REFERENCE (the default) or ASSEMBLY_RFC
+        for every later call that runs the message plan (decode_messages,
+        reply_messages, check_utf8_wire, reply_checked, reply_validated and
+        their _streams forms)."""
+        _check(self._L.wsg_set_assembly(self._ctx, int(mode)), "wsg_set_assembly")
+
+    @property
+    def assembly(self):
+        """The mode wsg_get_assembly reports."""
+        return int(self._L.wsg_get_assembly(self._ctx))
 
     # -- batch decode (unmask) ----------------------------------------------
     def decode_batch(self, wire, frame_start, out=None, info=None, stream=None):

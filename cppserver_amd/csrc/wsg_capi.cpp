@@ -235,6 +235,16 @@ int wsg_destroy(wsg_ctx* c)
     return WSG_OK;
 }
 
+int wsg_set_assembly(wsg_ctx* c, int mode)
+{
+    if (!c || (mode != WSG_ASSEMBLY_REFERENCE && mode != WSG_ASSEMBLY_RFC))
+        return WSG_EINVAL;
+    c->assembly = mode;
+    return WSG_OK;
+}
+
+int wsg_get_assembly(wsg_ctx* c) { return c ? c->assembly : WSG_EINVAL; }
+
 void* wsg_stream(wsg_ctx* c) { return c ? static_cast<void*>(c->stream) : nullptr; }
 
 int wsg_sync(wsg_ctx* c, void* stream)

@@ -36,17 +36,26 @@ inline uint64_t pieces_bound(uint32_t n, uint64_t wire_cap) { return wire_cap / 
 // this bound whatever the batch holds); a reply cuts the same frames at
 // 16-byte chunks of another destination.  Both are the context's: entered
 // behind the previous call's kernels, whatever stream they ran on.
-int msg_scratch(wsg_ctx* c, hipStream_t s, uint32_t n, uint64_t wire_len, wsg::MsgPlan* plan, uint64_t* pieces_cap,
+// Under WSG_ASSEMBLY_RFC the plan block holds that rule's scans behind the
+// reference rule's (which its reply kernels and the gather share).
+int msg_scratch(wsg_ctx* c, hipStream_t s, uint32_t n, uint64_t wire_len, wsg::MsgPlans* plans, uint64_t* pieces_cap,
                 bool* ordered)
 {
     *pieces_cap = pieces_bound(n, wire_len);
     if (*pieces_cap > UINT32_MAX)
         return WSG_EINVAL;
-    if (int rc = ensure_array(c->d_msg_plan, c->msg_plan_cap, wsg::msg_plan_layout(nullptr, n, nullptr)))
+    plans->assembly = c->assembly;
+    const bool rfc = c->assembly == WSG_ASSEMBLY_RFC;
+    const uint64_t ref_bytes = (wsg::msg_plan_layout(nullptr, n, nullptr) + 15) & ~uint64_t(15);
+    if (int rc = ensure_array(c->d_msg_plan, c->msg_plan_cap,
+                              ref_bytes + (rfc ? wsg::rfc_plan_layout(nullptr, n, nullptr) : 0)))
         return rc;
     if (int rc = ensure_array(c->d_msg_pieces, c->msg_pieces_cap, *pieces_cap))
         return rc;
-    wsg::msg_plan_layout(c->d_msg_plan, n, plan);
+    wsg::msg_plan_layout(c->d_msg_plan, n, &plans->ref);
+    plans->rfc = wsg::RfcPlan{};
+    if (rfc)
+        wsg::rfc_plan_layout(c->d_msg_plan + ref_bytes, n, &plans->rfc);
     return scratch_enter(c->msg_order, s, ordered);
 }
 
@@ -131,7 +140,7 @@ int wsg_decode_messages(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, co
          !in_alloc(d_info, uint64_t(n) * sizeof(wsg_recv_info))))
         return WSG_EINVAL;
     hipStream_t s = as_stream(stream);
-    wsg::MsgPlan plan;
+    wsg::MsgPlans plan;
     uint64_t pieces_cap;
     bool ordered = false;
     if (int rc = msg_scratch(c, s, n, wire_len, &plan, &pieces_cap, &ordered))
@@ -139,7 +148,7 @@ int wsg_decode_messages(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, co
     WSG_HIP(wsg::launch_msg_plan(s, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams, d_state, msg_cap,
                                  d_msgs, d_count, d_info, plan, c->d_msg_pieces, pieces_cap, c->d_err));
     if (n)
-        if (int rc = gather_launch(c, s, wsg::launch_msg_gather, d_wire, plan, pieces_cap, d_msg, msg_cap))
+        if (int rc = gather_launch(c, s, wsg::launch_msg_gather, d_wire, plan.ref, pieces_cap, d_msg, msg_cap))
             return rc;
     return scratch_leave(c->msg_order, s, ordered);
 }
@@ -198,7 +207,7 @@ int wsg_check_utf8_wire(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, co
          !in_alloc(d_result, 4 * 8)))
         return WSG_EINVAL;
     hipStream_t s = as_stream(stream);
-    wsg::MsgPlan plan;
+    wsg::MsgPlans plan;
     uint64_t pieces_cap;
     bool ordered = false;
     if (int rc = msg_scratch(c, s, n, wire_len, &plan, &pieces_cap, &ordered))
@@ -209,7 +218,7 @@ int wsg_check_utf8_wire(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, co
     WSG_HIP(wsg::launch_utf8_init(s, rec_grid, d_msgs, d_count, n, d_valid, d_result));
     if (n && which) {
         const int t = timing_begin(c, s);
-        WSG_HIP(wsg::launch_utf8_wire(s, utf8_wire_grid(c, pieces_cap), d_wire, wire_len, plan, c->d_msg_pieces,
+        WSG_HIP(wsg::launch_utf8_wire(s, utf8_wire_grid(c, pieces_cap), d_wire, wire_len, plan.ref, c->d_msg_pieces,
                                       pieces_cap, d_msgs, d_count, n, which, d_valid));
         timing_end(c, s, t);
     }
@@ -370,7 +379,7 @@ int wsg_reply_messages(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, con
          !in_alloc(d_info, uint64_t(n) * sizeof(wsg_recv_info))))
         return WSG_EINVAL;
     hipStream_t s = as_stream(stream);
-    wsg::MsgPlan plan;
+    wsg::MsgPlans plan;
     uint64_t pieces_cap;
     bool ordered = false;
     if (int rc = msg_scratch(c, s, n, wire_len, &plan, &pieces_cap, &ordered))
@@ -380,7 +389,7 @@ int wsg_reply_messages(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, con
                                    d_stream_reply, d_msgs, d_count, d_info, plan, c->d_msg_pieces, pieces_cap,
                                    c->d_err));
     if (n)
-        if (int rc = gather_launch(c, s, wsg::launch_reply_gather, d_wire, plan, pieces_cap, d_reply, reply_cap))
+        if (int rc = gather_launch(c, s, wsg::launch_reply_gather, d_wire, plan.ref, pieces_cap, d_reply, reply_cap))
             return rc;
     return scratch_leave(c->msg_order, s, ordered);
 }
@@ -459,7 +468,7 @@ int reply_checked(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const ui
     // both scratches are the context's: behind the last user of either,
     // whatever stream it ran on
     wsg::ProtoPlan pplan;
-    wsg::MsgPlan plan;
+    wsg::MsgPlans plan;
     uint64_t pieces_cap;
     bool ordered = false, pordered = false;
     wsg::Utf8Inside utf8{which, d_valid, d_utf8_result, nullptr, 1, 1};
@@ -476,7 +485,7 @@ int reply_checked(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const ui
                                            d_msgs, d_count, d_info, plan, pplan, c->d_msg_pieces, pieces_cap,
                                            c->d_err, validated ? &utf8 : nullptr));
     if (n)
-        if (int rc = gather_launch(c, s, wsg::launch_reply_gather, d_wire, plan, pieces_cap, d_reply, reply_cap))
+        if (int rc = gather_launch(c, s, wsg::launch_reply_gather, d_wire, plan.ref, pieces_cap, d_reply, reply_cap))
             return rc;
     if (int rc = scratch_leave(c->proto_order, s, pordered))
         return rc;

@@ -82,7 +82,8 @@ struct wsg_ctx {
     // scratch
     wsg_enc_scratch enc;
     wsg_scratch_order enc_order;   // wsg_encode_batch calls
-    // wsg_decode_messages: the plan block (wsg::msg_plan_layout) and the gather's piece records
+    // wsg_decode_messages: the plan block (wsg::msg_plan_layout, wsg::rfc_plan_layout behind it) and the gather's piece records
+    int assembly = WSG_ASSEMBLY_REFERENCE;   // wsg_set_assembly: the rule of the calls that run the message plan
     uint8_t* d_msg_plan = nullptr;
     uint64_t msg_plan_cap = 0;
     wsg::MsgPiece* d_msg_pieces = nullptr;

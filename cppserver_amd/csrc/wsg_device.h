@@ -1,5 +1,5 @@
 // wsg_device.h — device helpers shared by the kernel sources (wsg_kernels.hip,
-// wsg_messages.hip, wsg_frames.hip, wsg_utf8.hip, wsg_proto.hip): 16-byte loads
+// wsg_messages.hip, wsg_frames.hip, wsg_utf8.hip, wsg_proto.hip, wsg_assembly.hip): 16-byte loads
 // and stores, byte funnels, the frame parse, the block scan, the wave
 // reductions, the stream search, the error latch and the wsg_msg record codec.  Internal linkage: every source gets its own copy.
 #pragma once

@@ -1,6 +1,6 @@
 // wsg_internal.h — kernel geometry and kernel declarations shared by the
 // kernel sources (wsg_kernels.hip, wsg_messages.hip, wsg_frames.hip,
-// wsg_utf8.hip, wsg_proto.hip) and the C-ABI implementation (wsg_ctx.h).
+// wsg_utf8.hip, wsg_proto.hip, wsg_assembly.hip) and the C-ABI implementation (wsg_ctx.h).
 #pragma once
 
 #include "wsg_frame.h"
@@ -105,6 +105,61 @@ struct MsgPlan {
 };
 // Bytes of that block for n frames; plan (or null) gets the pointers into base.
 uint64_t msg_plan_layout(uint8_t* base, uint32_t n, MsgPlan* plan);
+// What WSG_ASSEMBLY_RFC adds to that scratch (wsg_assembly.hip), behind the
+// MsgPlan block.  A frame is of class D (a data frame: opcode 0-7, no error),
+// DF (D with FIN), C (a FIN control frame without error) or of none, and H
+// when it heads a stream; a run is the D frames from the first one behind a DF
+// frame or at or behind a stream's head to the next DF frame of that stream.
+// The frames' kernels know the streams through H alone, so every frame of a
+// run derives the same run from the same scans.  They share MsgPlan's sidx,
+// rex, brep*, brn, tot ([0] messages, [2] delivered bytes, [3] pieces) and
+// rtot with the reply kernels and the gather.
+struct RfcPlan {
+    // per frame, block-local (the batch-wide value: combined with the block's prefix)
+    uint32_t* cnt;        // n: frames before i of class D | DF << 8 | C << 16 | H << 24
+    uint32_t* qd;         // n: 1 + last DF frame < i (0: none)
+    uint32_t* hq;         // n: 1 + last H frame <= i (0: none)
+    uint32_t* pop;        // n: 1 + last D frame <= i that names an opcode (0: none)
+    uint32_t* ex;         // n: message-ending frames delivered before i
+    uint64_t* ab;         // n: delivered payload bytes before i
+    uint64_t* cb;         // n: ... of control frames
+    uint64_t* pc;         // n: pieces of the delivered frames before i | of the control frames among them << 32
+    // per frame, batch-wide
+    uint32_t* ff;         // n: a C frame inside a run, a DF frame: the run's first frame; else i
+    uint32_t* eo;         // n: the frame that ends frame i's message (i itself for a C frame); UINT32_MAX: not delivered
+    // nb each: block partials and their exclusive prefixes
+    uint32_t* bD;
+    uint32_t* bD_pre;
+    uint32_t* bDF;
+    uint32_t* bDF_pre;
+    uint32_t* bC;
+    uint32_t* bC_pre;
+    uint32_t* bH;
+    uint32_t* bH_pre;
+    uint32_t* bqd;
+    uint32_t* bqd_pre;
+    uint32_t* bhq;
+    uint32_t* bhq_pre;
+    uint32_t* bpop;
+    uint32_t* bpop_pre;
+    uint32_t* bex;
+    uint32_t* bex_pre;
+    uint64_t* bab;
+    uint64_t* bab_pre;
+    uint64_t* bcb;
+    uint64_t* bcb_pre;
+    uint64_t* bpc;
+    uint64_t* bpc_pre;
+    uint64_t* tot;        // [0] D frames, [1] DF frames, [2] C frames, [3] H frames, [4] last DF frame + 1
+};
+uint64_t rfc_plan_layout(uint8_t* base, uint32_t n, RfcPlan* plan);
+// Both plans of one call and the rule that picks between them (the context's
+// mode, read on the host when the call is made).
+struct MsgPlans {
+    MsgPlan ref;
+    RfcPlan rfc;
+    int assembly;         // WSG_ASSEMBLY_*
+};
 // One work piece of the gather, everything its wave needs in one 32-byte
 // scalar load (a piece -> frame map as the encode's put three dependent
 // loads between a wave's start and its first data load).
@@ -119,7 +174,7 @@ struct alignas(32) MsgPiece {
 // records (pieces_cap entries); latches frame errors and WSG_ENOMEM.
 hipError_t launch_msg_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
                            const uint32_t* stream_first, uint32_t n_streams, wsg_stream_state* state, uint64_t msg_cap,
-                           wsg_msg* msgs, uint64_t* count, wsg_recv_info* info, const MsgPlan& plan,
+                           wsg_msg* msgs, uint64_t* count, wsg_recv_info* info, const MsgPlans& plans,
                            MsgPiece* pieces, uint64_t pieces_cap, unsigned long long* err);
 // The gather pass: every delivered payload byte, unmasked, to its place in msg.
 hipError_t launch_msg_gather(hipStream_t s, int grid, const uint8_t* wire, const MsgPlan& plan,
@@ -139,7 +194,7 @@ hipError_t launch_reply_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_l
                              const uint32_t* stream_first, uint32_t n_streams, wsg_stream_state* state,
                              const ReplyRule& rule, const uint32_t* send_key, uint8_t* reply, uint64_t reply_cap,
                              uint64_t* reply_off, uint64_t* stream_reply, wsg_msg* msgs, uint64_t* count,
-                             wsg_recv_info* info, const MsgPlan& plan, MsgPiece* pieces, uint64_t pieces_cap,
+                             wsg_recv_info* info, const MsgPlans& plans, MsgPiece* pieces, uint64_t pieces_cap,
                              unsigned long long* err);
 // wsg_reply_checked's plan pass: launch_reply_plan with the protocol kernels
 // (launch_proto_* below, d_state's consumed written ahead of them) and the
@@ -157,12 +212,39 @@ hipError_t launch_reply_checked_plan(hipStream_t s, int stream_grid, const uint8
                                      const uint32_t* send_key, uint8_t* reply, uint64_t reply_cap, uint64_t* reply_off,
                                      uint64_t* stream_reply, uint64_t* close_off, wsg_proto_verdict* verdict,
                                      uint64_t* result, wsg_msg* msgs, uint64_t* count, wsg_recv_info* info,
-                                     const MsgPlan& plan, const ProtoPlan& pplan, MsgPiece* pieces,
+                                     const MsgPlans& plans, const ProtoPlan& pplan, MsgPiece* pieces,
                                      uint64_t pieces_cap, unsigned long long* err,
                                      const Utf8Inside* utf8 = nullptr);
 // k_msg_gather over those records: every replied payload byte, re-keyed, to its place in reply.
 hipError_t launch_reply_gather(hipStream_t s, int grid, const uint8_t* wire, const MsgPlan& plan,
                                const MsgPiece* pieces, uint64_t pieces_cap, uint8_t* reply, uint64_t reply_cap);
+
+// ---- WSG_ASSEMBLY_RFC (wsg_set_assembly; wsg_assembly.hip) ------------------
+// The plan kernels of RFC 6455 5.4's rule, in the places the launchers of
+// wsg_messages.hip run the reference rule's (n > 0 but for launch_rfc_state).
+// The four scan kernels: d_info and the error latch, P.sidx, R, P.tot,
+// d_count[0..1], WSG_ENOMEM (msg_cap); d_state[j].ahead is read.
+hipError_t launch_rfc_scans(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
+                            const uint32_t* stream_first, uint32_t n_streams, const wsg_stream_state* state,
+                            uint64_t msg_cap, uint64_t* count, wsg_recv_info* info, const MsgPlan& P, const RfcPlan& R,
+                            unsigned long long* err);
+// k_msg_finalize's part: d_msgs and the gather's piece records, in dense order.
+hipError_t launch_rfc_finalize(hipStream_t s, const uint8_t* wire, const wsg_recv_info* info, uint32_t n,
+                               const MsgPlan& P, const RfcPlan& R, wsg_msg* msgs, MsgPiece* pieces,
+                               uint64_t pieces_cap);
+// k_msg_state's part (consumed, opcode 0, ahead), or k_msg_consumed's (consumed alone); n == 0 allowed.
+hipError_t launch_rfc_state(hipStream_t s, uint32_t n, const uint32_t* stream_first, uint32_t n_streams,
+                            wsg_stream_state* state, const RfcPlan& R, bool consumed_only);
+// k_reply_local's and k_reply_finalize's parts, around k_reply_blocks.
+hipError_t launch_rfc_reply_local(hipStream_t s, bool checked, const uint8_t* wire, const wsg_recv_info* info,
+                                  uint32_t n, const MsgPlan& P, const RfcPlan& R, const ReplyRule& rule, wsg_msg* msgs,
+                                  const uint64_t* verdict);
+hipError_t launch_rfc_reply_finalize(hipStream_t s, bool checked, const wsg_recv_info* info, uint32_t n,
+                                     const uint32_t* stream_first, uint32_t n_streams, const MsgPlan& P,
+                                     const RfcPlan& R, const ReplyRule& rule, const uint32_t* send_key,
+                                     const wsg_msg* msgs, uint8_t* reply, uint64_t reply_cap, uint64_t* reply_off,
+                                     uint64_t* stream_reply, MsgPiece* pieces, uint64_t pieces_cap,
+                                     const uint64_t* verdict, uint64_t* close_off);
 
 // ---- the device framer (wsg_frame_streams; wsg_frames.hip) -----------------
 // Scratch of one call, carved out of one device array of uint64 (one block =
@@ -230,7 +312,7 @@ hipError_t launch_utf8_verdicts_over(hipStream_t s, int rec_grid, int stream_gri
 // without k_msg_state, so d_state is read (the sticky-opcode seed) and not written.
 hipError_t launch_msg_plan_only(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
                                 const uint32_t* stream_first, uint32_t n_streams, const wsg_stream_state* state,
-                                wsg_msg* msgs, uint64_t* count, wsg_recv_info* info, const MsgPlan& plan,
+                                wsg_msg* msgs, uint64_t* count, wsg_recv_info* info, const MsgPlans& plans,
                                 MsgPiece* pieces, uint64_t pieces_cap, unsigned long long* err);
 // What wsg_reply_validated adds to launch_reply_checked_plan: the UTF-8 check
 // from the wire between the protocol judge and the merge, on the dense piece

@@ -1,7 +1,7 @@
 // wsg_messages.hip — message assembly and replies on the device
 // (wsg_decode_messages, wsg_reply_messages, wsg_reply_checked): the plan
 // kernels, k_msg_gather and their launchers.
-#include "wsg_device.h"
+#include "wsg_msgplan.h"
 
 namespace wsg {
 
@@ -83,43 +83,6 @@ __device__ __forceinline__ uint32_t sticky_opcode(const MsgPlan& P, const wsg_re
     const uint32_t op = pv ? info[pv - 1].opcode : 0u;
     return op ? op : state[j].opcode;
 }
-
-__device__ __forceinline__ uint64_t msg_pieces_of(uint64_t bytes)
-{
-    return bytes ? (bytes + PIECE_ALIGN - 1 + PIECE - 1) / PIECE : 0;
-}
-
-__device__ __forceinline__ void put_piece(MsgPiece* p, uint64_t poff, uint64_t d0, uint64_t len, uint32_t key,
-                                          uint32_t k)
-{
-    static_assert(sizeof(MsgPiece) == 32 && offsetof(MsgPiece, len) == 16 && offsetof(MsgPiece, k) == 28, "MsgPiece");
-    v4u* w = reinterpret_cast<v4u*>(p);
-    w[0] = v4u{uint32_t(poff), uint32_t(poff >> 32), uint32_t(d0), uint32_t(d0 >> 32)};
-    w[1] = v4u{uint32_t(len), uint32_t(len >> 32), key, k};
-}
-
-// pieces[t] for t in [lo, hi) of every lane's frame (fill_tiles_wave's
-// scheme: a frame of many pieces is written by the whole wave).
-__device__ __forceinline__ void fill_pieces_wave(MsgPiece* pieces, uint64_t lo, uint64_t hi, uint64_t poff,
-                                                 uint64_t d0, uint64_t len, uint32_t key)
-{
-    const uint32_t lane = threadIdx.x & 63;
-    constexpr uint64_t kShort = 4;   // ranges up to this many pieces: the lane stores its own
-    if (hi > lo && hi - lo <= kShort)
-        for (uint64_t t = lo; t < hi; ++t)
-            put_piece(pieces + t, poff, d0, len, key, uint32_t(t - lo));
-    uint64_t pending = __ballot(hi > lo + kShort);
-    while (pending) {
-        const int j = __builtin_ctzll(pending);
-        pending &= pending - 1;
-        const uint64_t a = lane_bcast(lo, j), b = lane_bcast(hi, j);
-        const uint64_t pj = lane_bcast(poff, j), dj = lane_bcast(d0, j), lj = lane_bcast(len, j);
-        const uint32_t kj = __builtin_amdgcn_readlane(key, j);
-        for (uint64_t t = a + lane; t < b; t += 64)
-            put_piece(pieces + t, pj, dj, lj, kj, uint32_t(t - a));
-    }
-}
-
 
 // The message that FIN frame i ends (ws.cpp:411-452), as the wsg_msg fields.
 __device__ __forceinline__ MsgRec msg_at_fin(const uint8_t* __restrict__ wire, const wsg_recv_info* __restrict__ info,
@@ -344,62 +307,6 @@ __global__ __launch_bounds__(BLOCK) void k_msg_consumed(uint32_t n, const uint32
 // terminal frame t, lane t sizes and writes the stream's close frame, and the
 // per-stream lanes write d_close_off.  The close frame belongs to frame t as a
 // reply belongs to its FIN frame, so one scan places both.
-
-namespace {
-
-// What message r is answered with: the first header byte (0: nothing), the
-// data length and the status of the PrepareSendFrame call.
-struct ReplyOf {
-    uint8_t op;
-    uint64_t len;
-    int32_t status;
-};
-
-__device__ __forceinline__ ReplyOf reply_of(const ReplyRule& rule, uint32_t kind, uint32_t opcode, uint64_t len,
-                                            int32_t status)
-{
-    const uint8_t v = kind >= 1 && kind <= 4 ? rule.op[kind] : uint8_t(0);
-    ReplyOf r;
-    r.op = v == WSG_REPLY_SAME ? uint8_t(WSG_FIN | opcode) : v;
-    r.len = kind == WSG_CB_CLOSE ? 0 : len;   // a close reply carries the status and no data
-    r.status = kind == WSG_CB_CLOSE ? status : 0;
-    return r;
-}
-
-__device__ __forceinline__ uint64_t reply_size(const ReplyRule& rule, const ReplyOf& r)
-{
-    if (!r.op)
-        return 0;
-    const SendGeom g = send_geom(r.op, rule.mask != 0, r.len, r.status);
-    return g.hdr + g.body;
-}
-
-// Reply bytes of the FIN frames before frame k, for k in [0, n].
-__device__ __forceinline__ uint64_t reply_before(const MsgPlan& P, uint32_t n, uint32_t k)
-{
-    return k < n ? P.rex[k] + P.brep_pre[k / BLOCK] : P.rtot[2];
-}
-
-// ---- wsg_reply_checked: a stream's effective verdict, as the reply kernels read it
-// (one little-endian word: code, pad, status, the terminal frame on top; all
-// 0xFF: none, and then no frame index equals or exceeds its frame).
-__device__ __forceinline__ uint32_t verdict_frame(uint64_t v) { return uint32_t(v >> 32); }
-
-// The close frame a verdict is answered with: PrepareSendFrame(WSG_FIN | WSG_CLOSE,
-// mask, NULL, 0, status); 1005 never goes on the wire (RFC 6455 7.4.1).
-__device__ __forceinline__ int32_t close_status(uint64_t v)
-{
-    const int32_t s = int32_t((v >> 16) & 0xFFFFu);
-    return s == 1005 ? 1000 : s;
-}
-
-__device__ __forceinline__ uint64_t close_size(const ReplyRule& rule, uint64_t v)
-{
-    const SendGeom g = send_geom(uint8_t(WSG_FIN | WSG_CLOSE), rule.mask != 0, 0, close_status(v));
-    return g.hdr + g.body;
-}
-
-} // namespace
 
 // CHECKED (wsg_reply_checked): frame i sizes its reply only in front of its
 // stream's terminal frame t, and the close frame's size when i == t; the
@@ -694,22 +601,30 @@ uint64_t msg_plan_layout(uint8_t* base, uint32_t n, MsgPlan* plan)
     return c.at;
 }
 
-// What the two plans share: the scans up to k_msg_bytes_blocks and then
+// What the two plans share: the scans up to k_msg_bytes_blocks (under
+// WSG_ASSEMBLY_RFC: launch_rfc_scans, which reads seed[j].ahead) and then
 // finish(nb), or, for no frame (no message, every stream unchanged with
 // nothing consumed), the totals and count_words of d_count zeroed; k_msg_state
-// behind either.
+// (launch_rfc_state) behind either when `state` is given.
 template <class Finish>
 static hipError_t launch_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
                               const uint32_t* stream_first, uint32_t n_streams, wsg_stream_state* state,
-                              uint64_t msg_cap, uint64_t* count, uint32_t count_words, wsg_recv_info* info,
-                              const MsgPlan& plan, unsigned long long* err, Finish finish, bool write_state = true)
+                              const wsg_stream_state* seed, uint64_t msg_cap, uint64_t* count, uint32_t count_words,
+                              wsg_recv_info* info, const MsgPlans& plans, unsigned long long* err, Finish finish)
 {
+    const MsgPlan& plan = plans.ref;
+    const bool rfc = plans.assembly == WSG_ASSEMBLY_RFC;
     const uint32_t nb = uint32_t((uint64_t(n) + BLOCK - 1) / BLOCK);
+    hipError_t re = hipSuccess;   // of the other source's launchers (each has taken its launch's error)
     if (n == 0) {
         if (hipError_t e = hipMemsetAsync(plan.tot, 0, 4 * sizeof(uint64_t), s); e != hipSuccess)
             return e;
         if (hipError_t e = hipMemsetAsync(count, 0, count_words * sizeof(uint64_t), s); e != hipSuccess)
             return e;
+    } else if (rfc) {
+        re = launch_rfc_scans(s, wire, wire_len, fs, n, stream_first, n_streams, seed, msg_cap, count, info, plan,
+                              plans.rfc, err);
+        finish(nb);
     } else {
         k_msg_scan_local<<<nb, BLOCK, 0, s>>>(wire, wire_len, fs, n, stream_first, n_streams, info, plan, err);
         k_msg_scan_blocks<<<1, BLOCK, 0, s>>>(plan, nb, count);
@@ -717,35 +632,58 @@ static hipError_t launch_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_
         k_msg_bytes_blocks<<<1, BLOCK, 0, s>>>(plan, nb, n, msg_cap, count, err);
         finish(nb);
     }
-    if (n_streams && write_state)
-        k_msg_state<<<(n_streams + BLOCK - 1) / BLOCK, BLOCK, 0, s>>>(info, n, stream_first, n_streams, state, plan);
+    if (n_streams && state) {
+        if (rfc) {
+            if (hipError_t e = launch_rfc_state(s, n, stream_first, n_streams, state, plans.rfc, false);
+                re == hipSuccess)
+                re = e;
+        } else {
+            k_msg_state<<<(n_streams + BLOCK - 1) / BLOCK, BLOCK, 0, s>>>(info, n, stream_first, n_streams, state,
+                                                                           plan);
+        }
+    }
+    const hipError_t e = hipGetLastError();
+    return re != hipSuccess ? re : e;
+}
+
+// k_msg_finalize, or its part under WSG_ASSEMBLY_RFC.
+static hipError_t launch_finalize(hipStream_t s, uint32_t nb, const uint8_t* wire, const wsg_recv_info* info,
+                                  uint32_t n, const uint32_t* stream_first, const wsg_stream_state* state,
+                                  const MsgPlans& plans, wsg_msg* msgs, MsgPiece* pieces, uint64_t pieces_cap)
+{
+    if (plans.assembly == WSG_ASSEMBLY_RFC)
+        return launch_rfc_finalize(s, wire, info, n, plans.ref, plans.rfc, msgs, pieces, pieces_cap);
+    k_msg_finalize<<<nb, BLOCK, 0, s>>>(wire, info, n, stream_first, state, plans.ref, msgs, pieces, pieces_cap);
     return hipGetLastError();
 }
 
 hipError_t launch_msg_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
                            const uint32_t* stream_first, uint32_t n_streams, wsg_stream_state* state, uint64_t msg_cap,
-                           wsg_msg* msgs, uint64_t* count, wsg_recv_info* info, const MsgPlan& plan,
+                           wsg_msg* msgs, uint64_t* count, wsg_recv_info* info, const MsgPlans& plans,
                            MsgPiece* pieces, uint64_t pieces_cap, unsigned long long* err)
 {
-    return launch_plan(s, wire, wire_len, fs, n, stream_first, n_streams, state, msg_cap, count, 2, info, plan, err,
-                       [&](uint32_t nb) {
-                           k_msg_finalize<<<nb, BLOCK, 0, s>>>(wire, info, n, stream_first, state, plan, msgs, pieces,
-                                                               pieces_cap);
-                       });
+    hipError_t fe = hipSuccess;
+    const hipError_t e = launch_plan(s, wire, wire_len, fs, n, stream_first, n_streams, state, state, msg_cap, count, 2,
+                                     info, plans, err, [&](uint32_t nb) {
+                                         fe = launch_finalize(s, nb, wire, info, n, stream_first, state, plans, msgs,
+                                                              pieces, pieces_cap);
+                                     });
+    return fe != hipSuccess ? fe : e;
 }
 
-// (d_state is only read: k_msg_finalize takes the opcode seed from it, k_msg_state is left out)
+// (d_state is only read: the plan takes its seed from it, k_msg_state is left out)
 hipError_t launch_msg_plan_only(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
                                 const uint32_t* stream_first, uint32_t n_streams, const wsg_stream_state* state,
-                                wsg_msg* msgs, uint64_t* count, wsg_recv_info* info, const MsgPlan& plan,
+                                wsg_msg* msgs, uint64_t* count, wsg_recv_info* info, const MsgPlans& plans,
                                 MsgPiece* pieces, uint64_t pieces_cap, unsigned long long* err)
 {
-    return launch_plan(
-        s, wire, wire_len, fs, n, stream_first, n_streams, nullptr, UINT64_MAX, count, 2, info, plan, err,
-        [&](uint32_t nb) {
-            k_msg_finalize<<<nb, BLOCK, 0, s>>>(wire, info, n, stream_first, state, plan, msgs, pieces, pieces_cap);
-        },
-        false);
+    hipError_t fe = hipSuccess;
+    const hipError_t e = launch_plan(s, wire, wire_len, fs, n, stream_first, n_streams, nullptr, state, UINT64_MAX,
+                                     count, 2, info, plans, err, [&](uint32_t nb) {
+                                         fe = launch_finalize(s, nb, wire, info, n, stream_first, state, plans, msgs,
+                                                              pieces, pieces_cap);
+                                     });
+    return fe != hipSuccess ? fe : e;
 }
 
 hipError_t launch_msg_gather(hipStream_t s, int grid, const uint8_t* wire, const MsgPlan& plan,
@@ -759,9 +697,10 @@ hipError_t launch_reply_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_l
                              const uint32_t* stream_first, uint32_t n_streams, wsg_stream_state* state,
                              const ReplyRule& rule, const uint32_t* send_key, uint8_t* reply, uint64_t reply_cap,
                              uint64_t* reply_off, uint64_t* stream_reply, wsg_msg* msgs, uint64_t* count,
-                             wsg_recv_info* info, const MsgPlan& plan, MsgPiece* pieces, uint64_t pieces_cap,
+                             wsg_recv_info* info, const MsgPlans& plans, MsgPiece* pieces, uint64_t pieces_cap,
                              unsigned long long* err)
 {
+    const MsgPlan& plan = plans.ref;
     if (n == 0) {   // no reply either
         if (hipError_t e = hipMemsetAsync(plan.rtot, 0, 4 * sizeof(uint64_t), s); e != hipSuccess)
             return e;
@@ -771,17 +710,30 @@ hipError_t launch_reply_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_l
             e != hipSuccess)
             return e;
     }
+    hipError_t fe = hipSuccess;
+    const auto keep = [&fe](hipError_t e) {
+        if (fe == hipSuccess)
+            fe = e;
+    };
     // (no d_msg: its size, d_count[1], meets no capacity)
-    return launch_plan(s, wire, wire_len, fs, n, stream_first, n_streams, state, UINT64_MAX, count, 4, info, plan, err,
-                       [&](uint32_t nb) {
-                           k_reply_local<false><<<nb, BLOCK, 0, s>>>(wire, info, n, stream_first, state, plan, rule,
-                                                                     msgs, nullptr);
-                           k_reply_blocks<false><<<1, BLOCK, 0, s>>>(plan, nb, n, reply_cap, count, err);
-                           k_reply_finalize<false><<<nb, BLOCK, 0, s>>>(info, n, stream_first, n_streams, plan, rule,
-                                                                        send_key, msgs, reply, reply_cap, reply_off,
-                                                                        stream_reply, pieces, pieces_cap, nullptr,
-                                                                        nullptr);
-                       });
+    const hipError_t e = launch_plan(
+        s, wire, wire_len, fs, n, stream_first, n_streams, state, state, UINT64_MAX, count, 4, info, plans, err,
+        [&](uint32_t nb) {
+            if (plans.assembly == WSG_ASSEMBLY_RFC) {
+                keep(launch_rfc_reply_local(s, false, wire, info, n, plan, plans.rfc, rule, msgs, nullptr));
+                k_reply_blocks<false><<<1, BLOCK, 0, s>>>(plan, nb, n, reply_cap, count, err);
+                keep(launch_rfc_reply_finalize(s, false, info, n, stream_first, n_streams, plan, plans.rfc, rule,
+                                               send_key, msgs, reply, reply_cap, reply_off, stream_reply, pieces,
+                                               pieces_cap, nullptr, nullptr));
+                return;
+            }
+            k_reply_local<false><<<nb, BLOCK, 0, s>>>(wire, info, n, stream_first, state, plan, rule, msgs, nullptr);
+            k_reply_blocks<false><<<1, BLOCK, 0, s>>>(plan, nb, n, reply_cap, count, err);
+            k_reply_finalize<false><<<nb, BLOCK, 0, s>>>(info, n, stream_first, n_streams, plan, rule, send_key, msgs,
+                                                         reply, reply_cap, reply_off, stream_reply, pieces, pieces_cap,
+                                                         nullptr, nullptr);
+        });
+    return fe != hipSuccess ? fe : e;
 }
 
 hipError_t launch_reply_checked_plan(hipStream_t s, int stream_grid, const uint8_t* wire, uint64_t wire_len,
@@ -791,10 +743,12 @@ hipError_t launch_reply_checked_plan(hipStream_t s, int stream_grid, const uint8
                                      const uint32_t* send_key, uint8_t* reply, uint64_t reply_cap, uint64_t* reply_off,
                                      uint64_t* stream_reply, uint64_t* close_off, wsg_proto_verdict* verdict,
                                      uint64_t* result, wsg_msg* msgs, uint64_t* count, wsg_recv_info* info,
-                                     const MsgPlan& plan, const ProtoPlan& pplan, MsgPiece* pieces,
+                                     const MsgPlans& plans, const ProtoPlan& pplan, MsgPiece* pieces,
                                      uint64_t pieces_cap, unsigned long long* err, const Utf8Inside* utf8)
 {
-    hipError_t pe = hipSuccess;   // of the protocol launchers (each has taken its launch's error)
+    const MsgPlan& plan = plans.ref;
+    const bool rfc = plans.assembly == WSG_ASSEMBLY_RFC;
+    hipError_t pe = hipSuccess;   // of the other sources' launchers (each has taken its launch's error)
     const auto keep = [&pe](hipError_t e) {
         if (pe == hipSuccess)
             pe = e;
@@ -817,18 +771,21 @@ hipError_t launch_reply_checked_plan(hipStream_t s, int stream_grid, const uint8
             keep(launch_utf8_init(s, 1, msgs, count, 0, utf8->valid, utf8->result));
     }
     const hipError_t e = launch_plan(
-        s, wire, wire_len, fs, n, stream_first, n_streams, state, UINT64_MAX, count, 5, info, plan, err,
+        s, wire, wire_len, fs, n, stream_first, n_streams, state, state, UINT64_MAX, count, 5, info, plans, err,
         [&](uint32_t nb) {   // (n > 0, so n_streams > 0: the caller checks)
             const uint64_t* v = reinterpret_cast<const uint64_t*>(verdict);
-            k_msg_consumed<<<(n_streams + BLOCK - 1) / BLOCK, BLOCK, 0, s>>>(n, stream_first, n_streams, state, plan);
+            if (rfc)
+                keep(launch_rfc_state(s, n, stream_first, n_streams, state, plans.rfc, true));
+            else
+                k_msg_consumed<<<(n_streams + BLOCK - 1) / BLOCK, BLOCK, 0, s>>>(n, stream_first, n_streams, state,
+                                                                                  plan);
             keep(launch_proto_scan(s, info, n, stream_first, n_streams, proto, pplan, verdict, result));
             keep(launch_proto_judge(s, wire, wire_len, info, n, stream_first, state, proto, role, max_message, pplan,
                                     verdict));
             if (utf8) {
                 // wsg_reply_validated: the dense piece records (the reply's replace them below), the
                 // check from the wire over them, its verdicts beside the caller's
-                k_msg_finalize<<<nb, BLOCK, 0, s>>>(wire, info, n, stream_first, state, plan, msgs, pieces,
-                                                    pieces_cap);
+                keep(launch_finalize(s, nb, wire, info, n, stream_first, state, plans, msgs, pieces, pieces_cap));
                 keep(launch_utf8_init(s, utf8->rec_grid, msgs, count, n, utf8->valid, utf8->result));
                 if (utf8->which)
                     keep(launch_utf8_wire(s, utf8->wire_grid, wire, wire_len, plan, pieces, pieces_cap, msgs, count,
@@ -842,6 +799,14 @@ hipError_t launch_reply_checked_plan(hipStream_t s, int stream_grid, const uint8
             if (also)
                 keep(launch_proto_merge(s, stream_grid, n, stream_first, n_streams, also, verdict));
             keep(launch_proto_finish(s, stream_grid, n, stream_first, n_streams, state, proto, pplan, verdict, result));
+            if (rfc) {
+                keep(launch_rfc_reply_local(s, true, wire, info, n, plan, plans.rfc, rule, msgs, v));
+                k_reply_blocks<true><<<1, BLOCK, 0, s>>>(plan, nb, n, reply_cap, count, err);
+                keep(launch_rfc_reply_finalize(s, true, info, n, stream_first, n_streams, plan, plans.rfc, rule,
+                                               send_key, msgs, reply, reply_cap, reply_off, stream_reply, pieces,
+                                               pieces_cap, v, close_off));
+                return;
+            }
             k_reply_local<true><<<nb, BLOCK, 0, s>>>(wire, info, n, stream_first, state, plan, rule, msgs, v);
             k_reply_blocks<true><<<1, BLOCK, 0, s>>>(plan, nb, n, reply_cap, count, err);
             k_reply_finalize<true><<<nb, BLOCK, 0, s>>>(info, n, stream_first, n_streams, plan, rule, send_key, msgs,

@@ -57,10 +57,15 @@ MSG = np.dtype(
 )
 
 # wsg_stream_state: what a connection carries from one wsg_decode_messages
-# call to the next.
-STREAM_STATE = np.dtype([("consumed", "<u4"), ("opcode", "u1"), ("_pad", "u1", (3,))])
+# call to the next (opcode under ASSEMBLY_REFERENCE, ahead under ASSEMBLY_RFC).
+STREAM_STATE = np.dtype([("consumed", "<u4"), ("opcode", "u1"), ("_pad", "u1"), ("ahead", "<u2")])
 
-assert MSG.itemsize == 40 and STREAM_STATE.itemsize == 8
+assert MSG.itemsize == 40 and STREAM_STATE.itemsize == 8 and STREAM_STATE.fields["ahead"][1] == 6
+
+# wsg_set_assembly's modes (include/wsg_capi.h WSG_ASSEMBLY_*): the reference's
+# rule (ws.cpp:399-452), or RFC 6455 5.4 (control frames are messages of their own).
+ASSEMBLY_REFERENCE, ASSEMBLY_RFC = 0, 1
+AHEAD_CAP = 65535   # the most control frames STREAM_STATE.ahead counts
 
 # wsg_stream_span: one connection's bytes in a wsg_frame_streams batch.
 STREAM_SPAN = np.dtype([("off", "<u8"), ("len", "<u8"), ("consumed", "<u8"), ("need", "<u8")])
@@ -177,9 +182,92 @@ def frame_plan(wire, spans):
     return np.array(starts, dtype=np.uint64), np.array(first, dtype=np.uint64), out, count
 
 
-def message_plan(info, stream_first, state=None, payload=None):
+def _rfc_message_plan(info, stream_first, state, payload, ahead_cap):
+    """message_plan under ASSEMBLY_RFC: one sequential walk per stream."""
+    n_streams = len(stream_first) - 1
+    new_state = np.zeros(n_streams, dtype=STREAM_STATE)
+    seed = np.zeros(n_streams, dtype=STREAM_STATE) if state is None else np.asarray(state, dtype=STREAM_STATE)
+    kinds = {WS_CLOSE: CB_CLOSE, WS_PING: CB_PING, WS_PONG: CB_PONG}
+    msgs, used = [], 0
+
+    def bytes_of(k):
+        return bytes(payload[int(info["payload_off"][k]):][:int(info["len"][k])])
+
+    def deliver(j, first, last, frames, opcode, kind):
+        nonlocal used
+        size = int(sum(int(info["len"][k]) for k in frames))
+        m = np.zeros((), dtype=MSG)
+        m["off"], m["len"], m["stream"], m["first_frame"], m["nframes"] = used, size, j, first, last - first + 1
+        m["kind"], m["opcode"] = kind, opcode
+        if opcode == WS_CLOSE:
+            m["status"] = 1000
+            if size >= 2:                             # the status leaves the callback's data
+                m["off"], m["len"] = used + 2, size - 2
+                m["status"] = 0
+                if payload is not None:
+                    head = bytes_of(first)
+                    m["status"] = head[0] << 8 | head[1]
+        msgs.append(m)
+        used += size
+
+    for j in range(n_streams):
+        lo, hi = int(stream_first[j]), int(stream_first[j + 1])
+        ahead_in = int(seed["ahead"][j])
+        run, first_run, rank, held, data, opcode = None, True, 0, [], [], 0
+        for i in range(lo, hi):
+            op, fin = int(info["opcode"][i]), bool(info["fin"][i])
+            if info["error"][i] or (op & 8 and not fin):
+                continue                              # in no message, ends none
+            if op & 8:
+                if run is None:
+                    deliver(j, i, i, [i], op, kinds.get(op, 0))
+                    continue
+                r, rank = rank, rank + 1
+                if first_run and r < ahead_in:
+                    continue                          # an earlier call delivered it
+                if r < ahead_cap:
+                    deliver(j, i, i, [i], op, kinds.get(op, 0))
+                else:
+                    held.append(i)                    # past what `ahead` can count: with the run's FIN frame
+                continue
+            if run is None:
+                run, rank, held, data, opcode = i, 0, [], [], 0
+            data.append(i)
+            opcode = op or opcode
+            if fin:
+                for c in held:
+                    deliver(j, c, c, [c], int(info["opcode"][c]), kinds.get(int(info["opcode"][c]), 0))
+                deliver(j, run, i, data, opcode, CB_RECEIVED if opcode in (WS_TEXT, WS_BINARY) else 0)
+                run, first_run = None, False
+        if run is None:
+            new_state["consumed"][j] = hi - lo
+        else:
+            new_state["consumed"][j] = run - lo
+            new_state["ahead"][j] = min(rank, ahead_cap)
+    table = np.array(msgs, dtype=MSG) if msgs else np.zeros(0, dtype=MSG)
+    return table, np.array([len(msgs), used], dtype=np.uint64), new_state
+
+
+def message_frames(info, msgs, assembly=ASSEMBLY_REFERENCE):
+    """Per message of a message_plan table, the frames whose payloads make its
+    buffer, in order: every frame of its span, or under ASSEMBLY_RFC a control
+    frame alone, else the span's data frames without an error."""
+    info = np.asarray(info, dtype=RECV_INFO)
+    out = []
+    for m in np.asarray(msgs, dtype=MSG):
+        span = range(int(m["first_frame"]), int(m["first_frame"]) + int(m["nframes"]))
+        if assembly == ASSEMBLY_RFC and not int(m["opcode"]) & 8:
+            span = [k for k in span if not int(info["opcode"][k]) & 8 and not info["error"][k]]
+        out.append(list(span))
+    return out
+
+
+def message_plan(info, stream_first, state=None, payload=None, assembly=ASSEMBLY_REFERENCE, ahead_cap=AHEAD_CAP):
     """The plan pass of wsg_decode_messages restated on the host: which
-    frames make which messages (reference ws.cpp:399-452).
+    frames make which messages (reference ws.cpp:399-452; ``assembly`` =
+    ASSEMBLY_RFC: RFC 6455 5.4, the walk include/wsg_capi.h states, where the
+    state's ``ahead`` is read and written, its opcode written as 0, and
+    ``ahead_cap`` is the most it counts: 65535 on the device).
 
     ``info``: RECV_INFO of the batch's frames; ``stream_first``: n_streams + 1
     frame indices, stream j's frames are [stream_first[j], stream_first[j+1])
@@ -195,6 +283,8 @@ def message_plan(info, stream_first, state=None, payload=None):
     """
     info = np.asarray(info, dtype=RECV_INFO)
     stream_first = np.asarray(stream_first, dtype=np.int64)
+    if assembly == ASSEMBLY_RFC:
+        return _rfc_message_plan(info, stream_first, state, payload, ahead_cap)
     n_streams = len(stream_first) - 1
     new_state = np.zeros(n_streams, dtype=STREAM_STATE)
     if state is not None:
@@ -333,20 +423,23 @@ def utf8_plan(msgs, msg_bytes, which, msg_cap=None):
     return valid, np.array([invalid, lowest, checked, nbytes], dtype=np.uint64)
 
 
-def utf8_wire_plan(info, stream_first, state, payload, which):
+def utf8_wire_plan(info, stream_first, state, payload, which, assembly=ASSEMBLY_REFERENCE):
     """wsg_check_utf8_wire restated on the host: message_plan over the frame
     table, the dense message bytes gathered from ``payload`` (the batch with
     its payloads unmasked where they sit, wsg_decode_batch's output) and
     utf8_plan over them.  Returns (msgs, count, valid, result); ``state`` is
     only read."""
     info = np.asarray(info, dtype=RECV_INFO)
-    msgs, count, new_state = message_plan(info, stream_first, state, payload)
+    msgs, count, new_state = message_plan(info, stream_first, state, payload, assembly=assembly)
     sf = np.asarray(stream_first, dtype=np.int64)
     buf = np.asarray(payload, dtype=np.uint8)
     dense = []
-    for j in range(len(sf) - 1):   # the delivered frames: every stream's consumed ones, in order
-        for i in range(int(sf[j]), int(sf[j]) + int(new_state["consumed"][j])):
-            dense.append(buf[int(info["payload_off"][i]): int(info["payload_off"][i]) + int(info["len"][i])])
+    if assembly == ASSEMBLY_RFC:   # the messages' frames, in the messages' order
+        delivered = [i for frames in message_frames(info, msgs, assembly) for i in frames]
+    else:                          # every stream's consumed frames, in order
+        delivered = [i for j in range(len(sf) - 1) for i in range(int(sf[j]), int(sf[j]) + int(new_state["consumed"][j]))]
+    for i in delivered:
+        dense.append(buf[int(info["payload_off"][i]): int(info["payload_off"][i]) + int(info["len"][i])])
     dense = np.concatenate(dense) if dense else np.zeros(0, dtype=np.uint8)
     assert len(dense) == int(count[1])
     valid, result = utf8_plan(msgs, dense, which)

@@ -148,19 +148,69 @@ typedef struct wsg_msg {
     uint64_t len;          /* the callback's size (close: without the 2 status bytes)     */
     uint32_t stream;       /* index of the stream                                          */
     uint32_t first_frame;  /* index in d_frame_start of the message's first frame         */
-    uint32_t nframes;      /* frames accumulated into it (>= 1)                            */
+    uint32_t nframes;      /* frames accumulated into it (>= 1); WSG_ASSEMBLY_RFC: the span
+                              first_frame .. its FIN frame, control frames inside it counted */
     int32_t  status;       /* close: ws.cpp:431-439 (1000 when < 2 bytes); otherwise 0     */
     uint8_t  kind;         /* WSG_CB_*; 0 = no callback (unknown sticky opcode, Q6)        */
-    uint8_t  opcode;       /* _ws_opcode at the FIN frame                                  */
+    uint8_t  opcode;       /* _ws_opcode at the FIN frame; WSG_ASSEMBLY_RFC: the message's own */
     uint8_t  _pad[6];      /* written as 0 */
 } wsg_msg;                 /* 40 bytes */
 
 typedef struct wsg_stream_state {
     uint32_t consumed;     /* out: frames of this stream that went into messages          */
-    uint8_t  opcode;       /* in: _ws_opcode before the stream's first frame;
-                              out: _ws_opcode after its last consumed frame                */
-    uint8_t  _pad[3];      /* written as 0 */
+    uint8_t  opcode;       /* WSG_ASSEMBLY_REFERENCE: in: _ws_opcode before the stream's
+                              first frame; out: _ws_opcode after its last consumed frame.
+                              WSG_ASSEMBLY_RFC: ignored, written as 0 (the resubmitted
+                              tail begins with the frame that names its opcode)            */
+    uint8_t  _pad;         /* written as 0 */
+    uint8_t  ahead[2];     /* a 16-bit count, little-endian, at offset 6 (two bytes, so that
+                              the struct names only the types it named before; a caller
+                              that carries the record from call to call never reads it, and
+                              WSG_STREAM_AHEAD does for one that wants to).
+                              WSG_ASSEMBLY_RFC: in: FIN control frames behind the first
+                              frame of the resubmitted tail that an earlier call delivered;
+                              out: those behind the first frame of the tail this call
+                              leaves (at most 65535).  WSG_ASSEMBLY_REFERENCE: ignored,
+                              written as 0                                                  */
 } wsg_stream_state;        /* 8 bytes */
+#define WSG_STREAM_AHEAD(s) ((uint16_t)((s).ahead[0] | ((s).ahead[1] << 8)))
+
+/* ---- the assembly rule: which frames make a message ------------------------ */
+/* (Added without an ABI bump: symbols only, and a field in what was padding.)
+ * WSG_ASSEMBLY_REFERENCE, the default: ws.cpp:399-452 bit for bit.  Every FIN
+ * frame ends a message made of all its stream's frames since the previous FIN
+ * frame, control frames included, under the sticky _ws_opcode.
+ * WSG_ASSEMBLY_RFC: RFC 6455 5.4.  A FIN control frame is a message of its own
+ * (buffer: its payload; first_frame: itself; nframes 1; opcode: its own; kind
+ * by that opcode, 0 for a reserved one; a close's status, off and len by the
+ * two-byte rule of its own payload), also between the fragments of a data
+ * message.  A data message is the payloads of its run's data frames alone: the
+ * run is the non-control frames from the first one behind the previous data
+ * FIN frame to the next data FIN frame.  first_frame is the run's first frame,
+ * nframes the span up to its FIN frame (control frames inside it count, so
+ * first_frame + nframes - 1 is the FIN frame), opcode the last non-zero opcode
+ * among the run's frames (the first fragment's on a legal stream), kind
+ * WSG_CB_RECEIVED for opcodes 1 and 2, else 0.  A frame with an error, and a
+ * control frame without FIN, lie in no message and end none.  Messages,
+ * buffers and replies are in the order of the frames that end them, so a ping
+ * inside a message comes in front of it.
+ * Carry-over.  When a stream ends inside a run, consumed stops at the run's
+ * first frame; the control frames behind it were delivered in this call (the
+ * first 65535 of them: `ahead` counts no further, and the rest wait for the
+ * call that holds the run's FIN frame) and are skipped, by their count in
+ * d_state[j].ahead, when the tail comes back.  Without an open run every frame
+ * of the stream is consumed and ahead is 0.
+ * The mode is the context's, read on the host when a call is made; a captured
+ * graph keeps the mode it was captured under.  It is honoured by
+ * wsg_decode_messages, wsg_decode_streams, wsg_reply_messages,
+ * wsg_reply_streams, wsg_check_utf8_wire, wsg_reply_checked(_streams) and
+ * wsg_reply_validated(_streams); the calls that work on tables
+ * (wsg_check_utf8, wsg_utf8_verdicts, wsg_check_protocol, wsg_frame_streams)
+ * take either mode's.                                                        */
+#define WSG_ASSEMBLY_REFERENCE 0
+#define WSG_ASSEMBLY_RFC       1
+int wsg_set_assembly(wsg_ctx* ctx, int mode);   /* WSG_EINVAL for any other mode */
+int wsg_get_assembly(wsg_ctx* ctx);             /* the mode; WSG_EINVAL without a context */
 
 /* wsg_decode_batch's frames, assembled into messages (ws.cpp:399-452) and
  * packed densely: the layout wsg_encode_batch takes its payloads in.
@@ -178,7 +228,9 @@ typedef struct wsg_stream_state {
  * describes them (room for n), d_count[1] = bytes used in d_msg.  Frames
  * after a stream's last FIN frame are its tail: no byte of theirs is written,
  * d_state[j].consumed says where it begins, and the caller resubmits them at
- * the head of stream j in its next call with the returned d_state[j].opcode.
+ * the head of stream j in its next call with the returned d_state[j] (its
+ * opcode; under WSG_ASSEMBLY_RFC, which replaces the rule of this paragraph
+ * by the one stated at wsg_set_assembly, its ahead).
  * Asynchronous on `stream`.  Latched for wsg_sync: a frame error (as
  * wsg_decode_batch; the frame then counts as an empty non-FIN continuation),
  * or WSG_ENOMEM when the messages need more than msg_cap bytes: then no byte
@@ -314,7 +366,12 @@ int wsg_decode_streams(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
  * everything else is final.
  * Streams: the call uses the scratch of wsg_decode_messages and is ordered
  * with those calls across streams (see "Streams" above); the same capture
- * rule holds: run it once with the same n first.                            */
+ * rule holds: run it once with the same n first.
+ * Under WSG_ASSEMBLY_RFC the messages are that rule's (wsg_set_assembly): a
+ * reply belongs to the frame that ends its message, so a ping between
+ * fragments is answered ahead of the echo of the message around it, and that
+ * echo carries the data frames' bytes alone; run the uncaptured call under
+ * the mode the capture will use.                                             */
 #define WSG_REPLY_SAME 0xFF   /* reply opcode byte: WSG_FIN | the message's opcode */
 
 int wsg_reply_messages(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
@@ -427,7 +484,10 @@ int wsg_check_utf8(wsg_ctx* ctx, const uint8_t* d_msg, uint64_t msg_cap,
  * n_streams, d_count, d_result, d_stream_first), d_wire not 16-byte aligned,
  * any other operand not 8-byte aligned (4 for d_stream_first), and under
  * WSG_CHECK=1 for an operand too short for its allocation.  The timing hook
- * brackets the payload kernel.                                               */
+ * brackets the payload kernel.
+ * Under WSG_ASSEMBLY_RFC the messages are that rule's: a text message is
+ * checked over its own fragments' bytes, whatever control frames lie between
+ * them, and d_state[j].ahead is read in the place of its opcode.             */
 int wsg_check_utf8_wire(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
                         const uint64_t* d_frame_start, uint32_t n,
                         const uint32_t* d_stream_first, uint32_t n_streams,
@@ -611,7 +671,11 @@ int wsg_proto_judge(const wsg_recv_info* info, const uint8_t* wire, const wsg_pr
  * protocol plan's, and enters and leaves both orders, so it is ordered
  * against every other user of either (see "Streams" above); the capture rule
  * is the usual one: run it once uncaptured with the same n and n_streams
- * first.  The timing hook brackets the gather, as in wsg_reply_messages.     */
+ * first.  The timing hook brackets the gather, as in wsg_reply_messages.
+ * Under WSG_ASSEMBLY_RFC the messages and replies are that rule's; the
+ * terminal-frame cut, the close frame, d_stream_reply, d_close_off and the
+ * wire_len + 14 * n bound mean what they mean above (a message is answered
+ * when the frame that ends it lies in front of the terminal frame).          */
 #define WSG_PV_UTF8           13  /* wsg_utf8_verdicts: an invalid text message or close reason (1007) */
 
 int wsg_reply_checked(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
@@ -661,7 +725,7 @@ int wsg_utf8_verdicts(wsg_ctx* ctx, const wsg_msg* d_msgs, const uint64_t* d_cou
                       uint32_t which, const uint64_t* d_valid, uint32_t n_streams,
                       wsg_proto_verdict* d_also, void* stream);
 
-/* ---- validated replies: the conformant echo in one call -------------------- */
+/* ---- validated replies: the checked, validating echo in one call ------------ */
 /* (Added without an ABI bump: symbols only.)
  *
  * wsg_reply_checked with the UTF-8 check inside it.  Every output equals what
@@ -703,8 +767,14 @@ int wsg_reply_validated(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
 /* Raw bytes to validated replies: wsg_reply_checked_streams with
  * wsg_reply_validated (d_also NULL) in the place of wsg_reply_checked; the
  * same returns, the same lowering of d_span[j].consumed and the same refusal
- * while capturing; d_valid has room for frame_cap words.  An RFC 6455
- * conformant echo server's loop is this call and one wsg_sync.               */
+ * while capturing; d_valid has room for frame_cap words.  An echo server's
+ * loop is this call and one wsg_sync.  Under WSG_ASSEMBLY_RFC that server is
+ * RFC 6455 conformant for control frames between fragments too: a ping inside
+ * a fragmented message is answered in the round it arrives, ahead of the
+ * echo, the echo holds the message's bytes alone under the message's opcode,
+ * and text is validated over those bytes.  Under the default,
+ * WSG_ASSEMBLY_REFERENCE, such a ping's bytes join the message (the
+ * reference's behaviour).                                                    */
 int wsg_reply_validated_streams(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
                                 wsg_stream_span* d_span, uint32_t n_streams, wsg_stream_state* d_state,
                                 uint64_t* d_frame_start, uint32_t frame_cap, uint32_t* d_stream_first,

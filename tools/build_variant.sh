@@ -14,7 +14,7 @@ F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -I$root/include $*"
 csrc=$root/cppserver_amd/csrc
 $H $F -I$csrc -c ${KSRC:-$csrc/wsg_kernels.hip} -o k.o
 pobjs=
-for p in ${PSRC-$csrc/wsg_messages.hip $csrc/wsg_frames.hip $csrc/wsg_utf8.hip $csrc/wsg_proto.hip}; do
+for p in ${PSRC-$csrc/wsg_messages.hip $csrc/wsg_frames.hip $csrc/wsg_utf8.hip $csrc/wsg_proto.hip $csrc/wsg_assembly.hip}; do
     o=p_$(basename "$p" .hip).o
     $H $F -I$csrc -c "$p" -o "$o"
     pobjs="$pobjs $o"

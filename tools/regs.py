@@ -57,6 +57,10 @@ if __name__ == "__main__":
     for name, kernels in (("wsg_messages.hip", ("k_msg_gather", "k_msg_finalize", "k_reply_local<0>", "k_reply_blocks<0>",
                                                 "k_reply_finalize<0>", "k_msg_consumed", "k_reply_local<1>",
                                                 "k_reply_blocks<1>", "k_reply_finalize<1>")),
+                          ("wsg_assembly.hip", ("k_rfc_scan_local", "k_rfc_scan_blocks", "k_rfc_bytes_local",
+                                                "k_rfc_bytes_blocks", "k_rfc_finalize", "k_rfc_state<0>", "k_rfc_state<1>",
+                                                "k_rfc_reply_local<0>", "k_rfc_reply_local<1>",
+                                                "k_rfc_reply_finalize<0>", "k_rfc_reply_finalize<1>")),
                           ("wsg_frames.hip", ("k_frame_count", "k_frame_write")),
                           ("wsg_utf8.hip", ("k_utf8_init", "k_utf8_scan", "k_utf8_count", "k_utf8_verdict_seed", "k_utf8_verdicts",
                                             "k_utf8_wire", "k_utf8_also_seed")),
