@@ -22,6 +22,8 @@ from .layout import (  # noqa: F401  (re-exported)
     PV_CTRL_FRAGMENT, PV_CTRL_LONG, PV_DATA, PV_FRAME, PV_MASK, PV_NONE, PV_OPCODE, PV_RSV, PV_TOO_BIG, protocol_plan,
     PV_UTF8, checked_reply_plan, merge_verdicts, utf8_verdicts, utf8_wire_plan, validated_verdicts,
     AHEAD_CAP, ASSEMBLY_REFERENCE, ASSEMBLY_RFC, message_frames,
+    UP_ACCEPTED, UP_BAD_CONNECTION, UP_BAD_HTTP, UP_BAD_UPGRADE, UP_BAD_VERSION, UP_EMPTY_KEY, UP_INCOMPLETE,
+    UP_MISSING, UP_NOT_GET, UP_NOT_WEBSOCKET, UP_TOO_LONG, UPGRADE_DTYPE, UPGRADE_RESP_MAX, upgrade_plan,
 )
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -89,6 +91,8 @@ def lib(path=None):
         "wsg_utf8_valid_up_to": (u64, [vp, u64]),
         "wsg_check_protocol": (ci, [vp, vp, u64, vp, u32, vp, u32, vp, vp, u32, u64, vp, vp, vp]),
         "wsg_proto_judge": (ci, [vp, vp, vp, u32, u64, vp, ctypes.POINTER(ctypes.c_uint16)]),
+        "wsg_upgrade_streams": (ci, [vp, vp, u64, vp, u32, u64, vp, vp, u64, vp, vp, vp]),
+        "wsg_upgrade_judge": (ci, [vp, u64, u64, vp, vp, u32, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "wsg_encode_batch": (ci, [vp, vp, vp, u32, vp, u64, vp, vp]),
         "wsg_fanout_encode": (ci, [vp, vp, u64, vp, u32, ctypes.c_uint8, ci, vp, u64, vp]),
         "wsg_fanout_encode_many": (ci, [vp, vp, vp, vp, vp, u32, vp, u32, ci, vp, u64, vp, vp]),
@@ -207,6 +211,24 @@ def proto_judge(info, wire, before, role=PROTO_ANY, max_message=0):
     if rc < 0:
         raise WSGError(rc, "wsg_proto_judge")
     return rc, int(status.value), st[1].copy()
+
+
+def upgrade_judge(data, max_request=0, resp_cap=UPGRADE_RESP_MAX):
+    """wsg_upgrade_judge: one connection's first bytes judged on the host by
+    the rule the kernels run.  Returns (rc, record, resp, consumed, need): the
+    call's status (WSG_ENOMEM when the response needs more than ``resp_cap``
+    bytes), one UPGRADE_DTYPE record, the response bytes, and the span's
+    outputs."""
+    data = bytes(data)
+    rec = np.zeros(1, dtype=UPGRADE_DTYPE)
+    resp = np.zeros(max(int(resp_cap), 1), dtype=np.uint8)
+    consumed, need = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    rc = lib().wsg_upgrade_judge(data, len(data), int(max_request), _np_ptr(rec), _np_ptr(resp) if resp_cap else None,
+                                 int(resp_cap), ctypes.byref(consumed), ctypes.byref(need))
+    if rc not in (WSG_OK, WSG_ENOMEM):
+        raise WSGError(rc, "wsg_upgrade_judge")
+    sent = resp[: int(rec["resp_len"][0])].tobytes() if rc == WSG_OK else b""
+    return rc, rec[0].copy(), sent, int(consumed.value), int(need.value)
 
 
 class _Pinned:
@@ -510,6 +532,45 @@ class Codec:
                                        self._stream(stream))
         _check(rc, "wsg_frame_streams")
         return frame_start, stream_first, count
+
+    def upgrade_streams(self, wire, spans, resp_cap=None, max_request=0, stream=None, up=None, resp=None,
+                        resp_off=None, count=None):
+        """wsg_upgrade_streams: the upgrade request at the head of every stream
+        of ``spans`` (as in frame_streams: consumed and need out, in place)
+        judged on the device.  Returns (up, resp, resp_off, count): uint8
+        [n_streams * 32] UPGRADE_DTYPE records, the response bytes in stream
+        order (``resp_cap`` bytes of room; default n_streams *
+        UPGRADE_RESP_MAX, which always suffices), int64[n_streams + 1] their
+        exclusive prefix, and count int64[4] = [accepted, answered with a
+        400, incomplete, response bytes].  A total above ``resp_cap`` latches
+        WSG_ENOMEM (sync) with no byte of ``resp`` written."""
+        t = self._torch
+        ns = int(spans.numel()) // STREAM_SPAN.itemsize
+        if spans.element_size() != 1 or int(spans.numel()) != ns * STREAM_SPAN.itemsize:
+            raise WSGError(WSG_EINVAL, "upgrade_streams: spans must be uint8, n_streams * 32 bytes")
+        dev = wire.device
+        if resp_cap is None:
+            resp_cap = ns * UPGRADE_RESP_MAX if resp is None else int(resp.numel())
+        cap = int(resp_cap)
+        if up is None:
+            up = t.empty(max(ns, 1) * UPGRADE_DTYPE.itemsize, dtype=t.uint8, device=dev)
+        if resp is None:
+            resp = t.empty(max(cap, 1), dtype=t.uint8, device=dev)
+        if resp_off is None:
+            resp_off = t.empty(ns + 1, dtype=t.int64, device=dev)
+        if count is None:
+            count = t.empty(4, dtype=t.int64, device=dev)
+        if (int(up.numel()) * up.element_size() < ns * UPGRADE_DTYPE.itemsize or cap > int(resp.numel())
+                or resp.element_size() != 1 or resp_off.element_size() != 8 or int(resp_off.numel()) < ns + 1
+                or count.element_size() != 8 or int(count.numel()) < 4):
+            raise WSGError(WSG_EINVAL, "upgrade_streams: a buffer is smaller than the batch needs")
+        rc = self._L.wsg_upgrade_streams(self._ctx, ctypes.c_void_p(wire.data_ptr()), wire.numel(),
+                                         ctypes.c_void_p(spans.data_ptr()), ns, int(max_request),
+                                         ctypes.c_void_p(up.data_ptr()), ctypes.c_void_p(resp.data_ptr()), cap,
+                                         ctypes.c_void_p(resp_off.data_ptr()), ctypes.c_void_p(count.data_ptr()),
+                                         self._stream(stream))
+        _check(rc, "wsg_upgrade_streams")
+        return up, resp, resp_off, count
 
     def decode_streams(self, wire, spans, state=None, frame_start=None, frame_cap=None, stream_first=None,
                        msg=None, msg_cap=None, stream=None, msgs=None, count=None, info=None):

@@ -298,6 +298,40 @@ int wsg_frame_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_
     return scratch_leave(c->frame_order, s, ordered);
 }
 
+// The upgrade handshake: one wave per stream judges the request, a scan of the
+// response sizes, the accept values, the responses.  The framer's scratch and
+// its order: a connection is in front of one call or the other.
+int wsg_upgrade_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_stream_span* d_span,
+                        uint32_t n_streams, uint64_t max_request, wsg_upgrade* d_up, uint8_t* d_resp,
+                        uint64_t resp_cap, uint64_t* d_resp_off, uint64_t* d_count, void* stream)
+{
+    if (!c || !d_count || !d_resp_off || (wire_len && !d_wire) || (n_streams && (!d_span || !d_up)) ||
+        (resp_cap && !d_resp) || n_streams == UINT32_MAX)
+        return WSG_EINVAL;
+    if (!aligned16(d_wire) || !aligned16(d_resp) || !aligned8(d_span) || !aligned8(d_up) || !aligned8(d_resp_off) ||
+        !aligned8(d_count))
+        return WSG_EINVAL;
+    if (c->check && (!in_alloc(d_wire, (wire_len + 15) & ~uint64_t(15)) ||
+                     !in_alloc(d_span, uint64_t(n_streams) * sizeof(wsg_stream_span)) ||
+                     !in_alloc(d_up, uint64_t(n_streams) * sizeof(wsg_upgrade)) || !in_alloc(d_resp, resp_cap) ||
+                     !in_alloc(d_resp_off, (uint64_t(n_streams) + 1) * 8) || !in_alloc(d_count, 4 * 8)))
+        return WSG_EINVAL;
+    hipStream_t s = as_stream(stream);
+    if (int rc = ensure_array(c->d_frame_plan, c->frame_plan_cap, wsg::upgrade_plan_layout(nullptr, n_streams, nullptr)))
+        return rc;
+    wsg::UpgradePlan plan;
+    wsg::upgrade_plan_layout(c->d_frame_plan, n_streams, &plan);
+    bool ordered = false;
+    if (int rc = scratch_enter(c->frame_order, s, &ordered))
+        return rc;
+    const int t = n_streams ? timing_begin(c, s) : -1;
+    WSG_HIP(wsg::launch_upgrade_streams(s, grid_for(c, ceil_div(n_streams, wsg::BLOCK / 64), c->dec_blocks_per_cu),
+                                        d_wire, wire_len, d_span, n_streams, max_request, d_up, d_resp, resp_cap,
+                                        d_resp_off, d_count, plan, c->d_err));
+    timing_end(c, s, t);
+    return scratch_leave(c->frame_order, s, ordered);
+}
+
 namespace {
 
 // wsg_decode_streams and wsg_reply_streams: the framer, one synchronisation

@@ -1,7 +1,7 @@
 // wsg_device.h — device helpers shared by the kernel sources (wsg_kernels.hip,
-// wsg_messages.hip, wsg_frames.hip, wsg_utf8.hip, wsg_proto.hip, wsg_assembly.hip): 16-byte loads
+// wsg_messages.hip, wsg_frames.hip, wsg_utf8.hip, wsg_proto.hip, wsg_assembly.hip, wsg_upgrade.hip): 16-byte loads
 // and stores, byte funnels, the frame parse, the block scan, the wave
-// reductions, the stream search, the error latch and the wsg_msg record codec.  Internal linkage: every source gets its own copy.
+// reductions, the stream search, a _streams call's span, the error latch and the wsg_msg record codec.  Internal linkage: every source gets its own copy.
 #pragma once
 
 #include <type_traits>
@@ -100,6 +100,32 @@ __device__ __forceinline__ uint64_t uni(uint64_t x)
 {
     return uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(uint32_t(x)))) |
            (uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(uint32_t(x >> 32)))) << 32);
+}
+
+// One stream of a _streams call (wave-uniform).
+struct SpanIn {
+    uint64_t off, len;
+    bool ok;
+};
+
+// Span j as given and whether it may be walked: inside the wire, and not
+// starting before the end of span j - 1 where that one lies inside the wire.
+__device__ __forceinline__ SpanIn span_in(const wsg_stream_span* span, uint32_t j, uint64_t wire_len)
+{
+    static_assert(sizeof(wsg_stream_span) == 32 && offsetof(wsg_stream_span, consumed) == 16, "wsg_stream_span layout");
+    const uint64_t* w = reinterpret_cast<const uint64_t*>(span + j);
+    SpanIn s;
+    s.off = uni(w[0]);
+    s.len = uni(w[1]);
+    bool ok = s.off <= wire_len && s.len <= wire_len - s.off;
+    if (ok && j > 0) {
+        const uint64_t* p = reinterpret_cast<const uint64_t*>(span + (j - 1));
+        const uint64_t poff = uni(p[0]), plen = uni(p[1]);
+        if (poff <= wire_len && plen <= wire_len - poff && s.off < poff + plen)
+            ok = false;
+    }
+    s.ok = uni(uint32_t(ok)) != 0;
+    return s;
 }
 
 // Bytes [0, k) of a dword as a mask (k <= 0: none, k >= 4: all).

@@ -37,31 +37,6 @@ constexpr uint32_t FR_HALF = 64 * CHUNK;          // 1 KiB: a 16-B block per lan
 constexpr uint32_t FR_BLOCKS = 2 * FR_HALF / 16;  // 16-B blocks of a wave's ring
 static_assert((FR_BLOCKS & (FR_BLOCKS - 1)) == 0 && FR_HALF >= 32, "the ring index is a mask; a header spans two blocks");
 
-struct SpanIn {
-    uint64_t off, len;
-    bool ok;
-};
-
-// Span j as given and whether it may be walked: inside the wire, and not
-// starting before the end of span j - 1 where that one lies inside the wire.
-__device__ __forceinline__ SpanIn span_in(const wsg_stream_span* span, uint32_t j, uint64_t wire_len)
-{
-    static_assert(sizeof(wsg_stream_span) == 32 && offsetof(wsg_stream_span, consumed) == 16, "wsg_stream_span layout");
-    const uint64_t* w = reinterpret_cast<const uint64_t*>(span + j);
-    SpanIn s;
-    s.off = uni(w[0]);
-    s.len = uni(w[1]);
-    bool ok = s.off <= wire_len && s.len <= wire_len - s.off;
-    if (ok && j > 0) {
-        const uint64_t* p = reinterpret_cast<const uint64_t*>(span + (j - 1));
-        const uint64_t poff = uni(p[0]), plen = uni(p[1]);
-        if (poff <= wire_len && plen <= wire_len - poff && s.off < poff + plen)
-            ok = false;
-    }
-    s.ok = uni(uint32_t(ok)) != 0;
-    return s;
-}
-
 // The aligned 16-B block at wire offset a, nothing for a block past `end`
 // (end <= wire_len, and the wire is readable to the end of its last block).
 __device__ __forceinline__ v4u fr_load(const uint8_t* __restrict__ wire, uint64_t a, uint64_t end)

@@ -1,6 +1,6 @@
 // wsg_internal.h — kernel geometry and kernel declarations shared by the
 // kernel sources (wsg_kernels.hip, wsg_messages.hip, wsg_frames.hip,
-// wsg_utf8.hip, wsg_proto.hip, wsg_assembly.hip) and the C-ABI implementation (wsg_ctx.h).
+// wsg_utf8.hip, wsg_proto.hip, wsg_assembly.hip, wsg_upgrade.hip) and the C-ABI implementation (wsg_ctx.h).
 #pragma once
 
 #include "wsg_frame.h"
@@ -270,6 +270,25 @@ hipError_t launch_frame_streams(hipStream_t s, int grid, const uint8_t* wire, ui
 // stream's first frame that wsg_decode_messages left in the tail.
 hipError_t launch_frame_tail(hipStream_t s, wsg_stream_span* span, uint32_t ns, const uint64_t* frame_start,
                              const uint32_t* stream_first, const wsg_stream_state* state, uint32_t n);
+
+// ---- the upgrade handshake (wsg_upgrade_streams; wsg_upgrade.hip) -----------
+// Scratch of one call, carved out of the framer's device array (one block =
+// BLOCK streams).
+struct UpgradePlan {
+    uint64_t* ex;       // ns: block-local exclusive prefix of the streams' response bytes
+    uint64_t* bsum;     // 4 * nb: block sums of response bytes, accepted, rejected, incomplete streams
+    uint64_t* bpre;     // nb: exclusive prefixes of the first of those
+    uint64_t* tot;      // [0] response bytes
+    uint32_t* accept;   // 8 * ns: each accepted stream's 28 accept bytes
+};
+uint64_t upgrade_plan_layout(uint64_t* base, uint32_t ns, UpgradePlan* plan);
+// Parse (one wave per stream, grid-stride over `grid` blocks), scan, accept
+// values, responses: d_up, the spans' consumed / need, resp_off (ns + 1),
+// count (4) and, when they fit, the responses; latches span and capacity errors.
+hipError_t launch_upgrade_streams(hipStream_t s, int grid, const uint8_t* wire, uint64_t wire_len,
+                                  wsg_stream_span* span, uint32_t ns, uint64_t max_request, wsg_upgrade* up,
+                                  uint8_t* resp, uint64_t resp_cap, uint64_t* resp_off, uint64_t* count,
+                                  const UpgradePlan& plan, unsigned long long* err);
 
 // ---- UTF-8 on the device (wsg_check_utf8; wsg_utf8.hip) ---------------------
 // k_utf8_init: d_valid[m] = len for m < min(d_count[0], msg_room), and

@@ -2,8 +2,8 @@
 
 numpy structured dtypes whose byte layout is exactly ``wsg_send_desc``,
 ``wsg_recv_info``, ``wsg_msg``, ``wsg_stream_state``, ``wsg_stream_span``,
-``wsg_proto_state`` and ``wsg_proto_verdict``, and the plans of the device
-entry points restated on the host;
+``wsg_proto_state``, ``wsg_proto_verdict`` and ``wsg_upgrade``, and the plans of
+the device entry points restated on the host;
 importing this module loads no native code.
 """
 import numpy as np
@@ -684,3 +684,160 @@ def checked_reply_plan(msgs, verdict, reply_op, mask, send_keys=None, n_streams=
     close_off[closing] = before(close_frame).astype(np.uint64)
     count = np.array([total, int((sizes > 0).sum()) + len(closing), len(closing)], dtype=np.uint64)
     return reply_off, stream_reply, close_off, count
+
+
+# ---- the upgrade handshake (wsg_upgrade_streams) -----------------------------
+UPGRADE_DTYPE = np.dtype([("key_off", "<u8"), ("url_off", "<u8"), ("key_len", "<u4"), ("url_len", "<u4"),
+                          ("resp_len", "<u4"), ("status", "<u2"), ("code", "u1"), ("_pad", "u1")])
+(UP_INCOMPLETE, UP_ACCEPTED, UP_BAD_HTTP, UP_BAD_CONNECTION, UP_BAD_UPGRADE, UP_EMPTY_KEY, UP_BAD_VERSION, UP_MISSING,
+ UP_NOT_GET, UP_NOT_WEBSOCKET, UP_TOO_LONG) = range(11)
+UPGRADE_RESP_MAX = 196
+WS_GUID = b"258EAFA5-E914-47DA-95CA-C5AB0DC85B11"
+_UP_TEXT = {
+    UP_BAD_HTTP: b"Invalid HTTP request",
+    UP_BAD_CONNECTION: b"Invalid WebSocket handshaked request: 'Connection' header value must be 'Upgrade' or "
+                       b"'keep-alive, Upgrade'",
+    UP_BAD_UPGRADE: b"Invalid WebSocket handshaked request: 'Upgrade' header value must be 'websocket'",
+    UP_EMPTY_KEY: b"Invalid WebSocket handshaked request: 'Sec-WebSocket-Key' header value must be non empty",
+    UP_BAD_VERSION: b"Invalid WebSocket handshaked request: 'Sec-WebSocket-Version' header value must be '13'",
+    UP_MISSING: b"Invalid WebSocket response",
+}
+
+
+def ws_accept(key):
+    """Base64(SHA-1(key || GUID)): the Sec-WebSocket-Accept value of ``key``."""
+    import base64
+    import hashlib
+
+    return base64.b64encode(hashlib.sha1(bytes(key) + WS_GUID).digest())
+
+
+def upgrade_response(code, key=b""):
+    """The bytes HTTPResponse serialises for an outcome (b"" when it gets none)."""
+    if code == UP_ACCEPTED:
+        return (b"HTTP/1.1 101 Switching Protocols\r\nConnection: Upgrade\r\nUpgrade: websocket\r\n"
+                b"Sec-WebSocket-Accept: " + ws_accept(key) + b"\r\nContent-Length: 0\r\n\r\n")
+    text = _UP_TEXT.get(code)
+    if text is None:
+        return b""
+    return (b"HTTP/1.1 400 Bad Request\r\nContent-Type: text/plain; charset=UTF-8\r\nContent-Length: %d\r\n\r\n%s"
+            % (len(text), text))
+
+
+def _lower(b):
+    return bytes(c + 32 if 65 <= c <= 90 else c for c in b)   # ASCII only, as tolower in the C locale
+
+
+def upgrade_judge(data, max_request=0):
+    """One connection's first bytes as WSSession::onReceived, HTTPRequest::Parse
+    and WebSocket::PerformServerUpgrade judge them.  Returns a dict: code,
+    status, consumed, need, key (offset, length), url (offset, length), resp."""
+    data = bytes(data)
+    out = dict(code=UP_TOO_LONG if max_request and len(data) >= max_request else UP_INCOMPLETE, status=0, consumed=0,
+               need=0, key=(0, 0), url=(0, 0), resp=b"")
+    p = data.find(b"\r\n\r\n")
+    if p < 0:
+        return out
+    hend = p + 4
+    eol = data.find(b"\r\n")
+    line = data[:eol]
+    s1, s2 = line.find(b" "), line.rfind(b" ")
+    bad = s1 < 0 or s1 == s2
+    headers, clen, at = [], 0, eol + 2
+    block_end = max(hend - 2, at)
+    while not bad and at < block_end:
+        e = data.find(b"\r\n", at, block_end)
+        e = block_end if e < 0 else e
+        ln = data[at:e]
+        if ln:
+            colon = ln.find(b":")
+            if colon <= 0:
+                bad = True
+                break
+            k, v = ln[:colon].strip(b" \t"), ln[colon + 1:].strip(b" \t")
+            v_at = at + colon + 1 + (len(ln[colon + 1:]) - len(ln[colon + 1:].lstrip(b" \t")))
+            headers.append((_lower(k), v, v_at))
+            if _lower(k) == b"content-length":
+                clen = 0
+                for c in v:
+                    if not 48 <= c <= 57:
+                        bad = True
+                        break
+                    clen = (clen * 10 + c - 48) % 2**64
+        at = e + 2
+    if bad:
+        out.update(code=UP_BAD_HTTP, status=400, consumed=hend, resp=upgrade_response(UP_BAD_HTTP))
+        return out
+    if len(data) - hend < clen:
+        out["need"] = min(hend + clen, U64_MAX)
+        return out
+    out.update(code=UP_NOT_GET, consumed=hend + clen, url=(s1 + 1, s2 - s1 - 1))
+    if line[:s1] != b"GET":
+        return out
+    seen, fail, key = set(), 0, None
+    for k, v, v_at in headers:
+        if k == b"connection":
+            squeezed = bytes(c for c in v if c not in b" \t\n\v\f\r")
+            if _lower(v) != b"upgrade" and _lower(squeezed) != b"keep-alive,upgrade":
+                fail = UP_BAD_CONNECTION
+        elif k == b"upgrade":
+            if _lower(v) != b"websocket":
+                fail = UP_BAD_UPGRADE
+        elif k == b"sec-websocket-key":
+            if not v:
+                fail = UP_EMPTY_KEY
+            else:
+                key = (v_at, len(v))
+        elif k == b"sec-websocket-version":
+            if v != b"13":
+                fail = UP_BAD_VERSION
+        else:
+            continue
+        if fail:
+            break
+        seen.add(k)
+    if key is not None:
+        out["key"] = key
+    if not seen:                 # whatever failed: none of the four in front of it
+        code = UP_NOT_WEBSOCKET
+    elif len(seen) != 4:
+        code = fail or UP_MISSING
+    else:                        # all four in front of a failing header: that one no longer counts
+        code = UP_ACCEPTED
+    resp = upgrade_response(code, data[key[0]:key[0] + key[1]] if key else b"")
+    out.update(code=code, resp=resp, status=101 if code == UP_ACCEPTED else 400 if resp else 0)
+    return out
+
+
+def upgrade_plan(wire, spans, max_request=0):
+    """wsg_upgrade_streams restated on the host: one request per stream
+    ``wire[off, off + len)``.  Returns (up, consumed, need, resp_off, resp,
+    count, bad): UPGRADE_DTYPE records, the spans' outputs, the exclusive
+    prefix of resp_len (n_streams + 1), the response bytes in stream order,
+    count = [accepted, answered with a 400, incomplete, response bytes], and
+    the spans latched as WSG_EINVAL (bad_spans)."""
+    wire = np.asarray(wire, dtype=np.uint8)
+    spans = np.asarray(spans, dtype=STREAM_SPAN)
+    ns = len(spans)
+    bad = bad_spans(len(wire), spans)
+    up = np.zeros(ns, dtype=UPGRADE_DTYPE)
+    consumed = np.zeros(ns, dtype=np.uint64)
+    need = np.zeros(ns, dtype=np.uint64)
+    resp_off = np.zeros(ns + 1, dtype=np.uint64)
+    resp = []
+    for j in range(ns):
+        if not bad[j]:
+            off, length = int(spans["off"][j]), int(spans["len"][j])
+            o = upgrade_judge(wire[off:off + length].tobytes(), max_request)
+            u = up[j]
+            u["code"], u["status"], u["resp_len"] = o["code"], o["status"], len(o["resp"])
+            if o["key"][1]:
+                u["key_off"], u["key_len"] = off + o["key"][0], o["key"][1]
+            if o["code"] not in (UP_INCOMPLETE, UP_TOO_LONG, UP_BAD_HTTP):
+                u["url_off"], u["url_len"] = off + o["url"][0], o["url"][1]
+            consumed[j], need[j] = o["consumed"], o["need"]
+            resp.append(o["resp"])
+        resp_off[j + 1] = resp_off[j] + np.uint64(up["resp_len"][j])
+    count = np.array([np.sum(up["code"] == UP_ACCEPTED), np.sum(up["status"] == 400),
+                      np.sum(up["code"] == UP_INCOMPLETE), resp_off[ns]], dtype=np.uint64)
+    return up, consumed, need, resp_off, np.frombuffer(b"".join(resp), dtype=np.uint8), count, bad

@@ -604,6 +604,98 @@ int wsg_check_protocol(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
 int wsg_proto_judge(const wsg_recv_info* info, const uint8_t* wire, const wsg_proto_state* before,
                     uint32_t role, uint64_t max_message, wsg_proto_state* after, uint16_t* status);
 
+/* ---- the upgrade handshake: a connection's first bytes on the device ------- */
+/* (Added without an ABI bump, as wsg_decode_messages was: symbols, a struct
+ * and constants only.)
+ *
+ * A connection's first bytes are its HTTP upgrade request.  wsg_upgrade_streams
+ * judges one request per stream exactly as WSSession::onReceived,
+ * HTTPRequest::Parse and WebSocket::PerformServerUpgrade do (csrc/wsg_upgrade.h
+ * restates them) and writes the bytes to send back.
+ * The rule.  The header block ends behind the first "\r\n\r\n" (hend); without
+ * one the request is incomplete.  The request line runs to the first "\r\n";
+ * with no space in it, or one only, the request is malformed.  The header
+ * lines in between are split at "\r\n" (a lone '\r' or '\n' is an ordinary
+ * byte); a line with no ':' or with ':' first is malformed; key and value are
+ * trimmed of space and tab.  Content-Length (name compared without case, the
+ * last one wins, a non-digit is malformed, the value taken mod 2^64) gives
+ * clen.  Malformed: 400 "Invalid HTTP request", consumed = hend, decided before
+ * the body's completeness.  Fewer than clen bytes behind hend: incomplete.
+ * Else consumed = hend + clen, and the bytes behind it are the connection's
+ * first frames.  A method other than "GET" gets no response.  Then the headers
+ * in order, names compared without case (ASCII): Connection must be "Upgrade",
+ * or "keep-alive,Upgrade" once space, \t, \n, \v, \f and \r are removed;
+ * Upgrade must be "websocket"; Sec-WebSocket-Key non-empty;
+ * Sec-WebSocket-Version "13".  The first failing header ends the walk.  Of
+ * the four, counting those in front of it: none seen, not a WebSocket request,
+ * no response (whatever failed); all four seen, the 101 response (a failing
+ * header behind them no longer counts), its accept value
+ * Base64(SHA-1(key || GUID)) over the last Sec-WebSocket-Key value in front of
+ * the end of the walk, of any length; otherwise a 400, with the failing
+ * header's text, or "Invalid WebSocket response" when none failed.           */
+#define WSG_UP_INCOMPLETE      0   /* no header end yet, or the body is short: resubmit with more bytes */
+#define WSG_UP_ACCEPTED        1   /* 101 */
+#define WSG_UP_BAD_HTTP        2   /* 400: malformed request line or header line */
+#define WSG_UP_BAD_CONNECTION  3   /* 400 */
+#define WSG_UP_BAD_UPGRADE     4   /* 400 */
+#define WSG_UP_EMPTY_KEY       5   /* 400 */
+#define WSG_UP_BAD_VERSION     6   /* 400 */
+#define WSG_UP_MISSING         7   /* 400: some of the four headers, not all */
+#define WSG_UP_NOT_GET         8   /* no response: the HTTP layer's */
+#define WSG_UP_NOT_WEBSOCKET   9   /* no response: none of the four headers in front of the walk's end */
+#define WSG_UP_TOO_LONG       10   /* incomplete at max_request bytes or more: no response, disconnect */
+#define WSG_UPGRADE_RESP_MAX 196   /* the longest response (the 'Connection' 400); the 101 has 148 bytes */
+
+typedef struct wsg_upgrade {      /* 32 bytes */
+    uint64_t key_off;   /* absolute wire offset of the trimmed Sec-WebSocket-Key value hashed; 0 if none */
+    uint64_t url_off;   /* absolute offset of the request target (for routing / onWSConnecting)          */
+    uint32_t key_len, url_len;
+    uint32_t resp_len;  /* bytes of this stream's response, 0 when it gets none                          */
+    uint16_t status;    /* 101, 400 or 0                                                                 */
+    uint8_t  code;      /* WSG_UP_*                                                                      */
+    uint8_t  _pad;      /* written as 0 */
+} wsg_upgrade;
+
+/* Stream j is d_wire[off, off + len) of d_span[j], one request per stream per
+ * call: whatever follows `consumed` is not looked at.  d_up[j]: the outcome;
+ * url_off / url_len are set when the request is whole and well-formed HTTP
+ * (codes other than INCOMPLETE, TOO_LONG and BAD_HTTP), key_off / key_len when
+ * the header walk met a key in front of its end; a length saturates at
+ * UINT32_MAX.  d_span[j].consumed: 0 while the request is incomplete (or too
+ * long), hend for BAD_HTTP, hend + clen otherwise.  d_span[j].need: hend +
+ * clen, saturating, when only the body is missing, else 0.
+ * max_request: 0 for no limit; otherwise an incomplete request of len >=
+ * max_request gets WSG_UP_TOO_LONG.
+ * Responses lie in stream order in d_resp; d_resp_off[0..n_streams] is the
+ * exclusive prefix of resp_len.  n_streams * WSG_UPGRADE_RESP_MAX always
+ * suffices for resp_cap.  When the total exceeds resp_cap no byte of d_resp
+ * is written and WSG_ENOMEM is latched (key n_streams << 8 | code); every
+ * table is still final.  d_count[0..4): streams accepted, answered with a
+ * 400, WSG_UP_INCOMPLETE, and the response bytes.
+ * A span past wire_len, or one that starts before the end of the span before
+ * it, is latched as wsg_frame_streams latches it (WSG_EINVAL under stream <<
+ * 8 | code); that stream gets WSG_UP_INCOMPLETE, consumed 0 and no response.
+ * n_streams == 0 and empty streams are valid.  WSG_EINVAL for a NULL operand,
+ * d_wire or d_resp not 16-byte aligned (d_wire readable to the end of its
+ * last 16-byte block), another operand not 8-byte aligned.
+ * Asynchronous on `stream`.  The call uses wsg_frame_streams' scratch of the
+ * ctx and is ordered across streams with those calls, under the same capture
+ * rule: run it once uncaptured with the same n_streams before capturing.
+ * The onWSConnecting veto stays the caller's: drop the response and route by
+ * url_off / url_len.                                                         */
+int wsg_upgrade_streams(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
+                        wsg_stream_span* d_span, uint32_t n_streams, uint64_t max_request,
+                        wsg_upgrade* d_up, uint8_t* d_resp, uint64_t resp_cap,
+                        uint64_t* d_resp_off /* n_streams + 1 */, uint64_t* d_count /* 4 */, void* stream);
+
+/* One request judged on the host by the rule the kernels run (host memory, no
+ * ctx, no OpenSSL): buf[0, len) as one stream at offset 0.  *out as d_up[j],
+ * the response to resp (resp_cap bytes of room; WSG_ENOMEM, with *out,
+ * *consumed and *need still written, when it is longer), *consumed and *need
+ * as the span's.  resp may be NULL with resp_cap 0.                          */
+int wsg_upgrade_judge(const uint8_t* buf, uint64_t len, uint64_t max_request, wsg_upgrade* out,
+                      uint8_t* resp, uint32_t resp_cap, uint64_t* consumed, uint64_t* need);
+
 /* ---- checked replies: an echo server that fails connections on the device -- */
 /* (Added without an ABI bump, as wsg_decode_messages was: symbols and
  * constants only.)

@@ -1,8 +1,8 @@
 """Register/occupancy report for k_decode and source variants with paths cut
 out (which path sets the kernel's VGPR count), and for k_msg_gather
 (wsg_decode_messages; wsg_reply_messages runs it too), the reply plan, the
-framer, the UTF-8 check (dense and from the wire), the protocol check and
-the checked reply (wsg_reply_checked).  Compiles for gfx950 only (no GPU needed).
+framer, the UTF-8 check (dense and from the wire), the protocol check,
+the checked reply (wsg_reply_checked) and the upgrade handshake (wsg_upgrade_streams).  Compiles for gfx950 only (no GPU needed).
 
 usage: python tools/regs.py
 """
@@ -65,7 +65,9 @@ if __name__ == "__main__":
                           ("wsg_utf8.hip", ("k_utf8_init", "k_utf8_scan", "k_utf8_count", "k_utf8_verdict_seed", "k_utf8_verdicts",
                                             "k_utf8_wire", "k_utf8_also_seed")),
                           ("wsg_proto.hip", ("k_proto_local", "k_proto_blocks", "k_proto_judge", "k_proto_finish",
-                                             "k_proto_merge"))):
+                                             "k_proto_merge")),
+                          ("wsg_upgrade.hip", ("k_upgrade_parse", "k_upgrade_scan_local", "k_upgrade_scan_blocks",
+                                               "k_upgrade_accept", "k_upgrade_respond"))):
         src = source(name)
         for k in kernels:
             base, _, flag = k.partition("<")   # name<0|1>: an instantiation of a template on one bool
