@@ -1,6 +1,7 @@
-// wsg_device.h — device helpers shared by the kernel sources (wsg_kernels.hip,
+// wsg_device.h — device helpers shared by the kernel sources (wsg_decode.hip,
+// wsg_encode.hip, wsg_fanout.hip, wsg_lane_device.hip, wsg_misc.hip,
 // wsg_messages.hip, wsg_frames.hip, wsg_utf8.hip, wsg_proto.hip, wsg_assembly.hip, wsg_upgrade.hip): 16-byte loads
-// and stores, byte funnels, the frame parse, the block scan, the wave
+// and stores, byte funnels and shifts, the output tile, the frame parse, the block scan, the wave
 // reductions, the stream search, a _streams call's span, the error latch and the wsg_msg record codec.  Internal linkage: every source gets its own copy.
 #pragma once
 
@@ -63,6 +64,55 @@ __device__ __forceinline__ v4u funnel(v4u lo, v4u hi, uint32_t s)
     }
     return r;
 }
+
+// 128-bit byte shifts and byte masks (runtime counts) built on funnel().
+__device__ __forceinline__ v4u shr_bytes(v4u x, uint64_t o)   // byte j = x[j + o]
+{
+    return o >= CHUNK ? v4u{0, 0, 0, 0} : funnel(x, v4u{0, 0, 0, 0}, uint32_t(o));
+}
+__device__ __forceinline__ v4u shl_bytes(v4u x, uint64_t s)   // byte j = x[j - s]
+{
+    return s == 0 ? x : s >= CHUNK ? v4u{0, 0, 0, 0} : funnel(v4u{0, 0, 0, 0}, x, uint32_t(CHUNK - s));
+}
+__device__ __forceinline__ v4u low_bytes(uint64_t n)   // bytes [0, n) = 0xFF
+{
+    const uint64_t lo = n >= 8 ? ~uint64_t(0) : (uint64_t(1) << (8 * n)) - 1;
+    const uint64_t hi = n >= 16 ? ~uint64_t(0) : n <= 8 ? 0 : (uint64_t(1) << (8 * (n - 8))) - 1;
+    return v4u{uint32_t(lo), uint32_t(lo >> 32), uint32_t(hi), uint32_t(hi >> 32)};
+}
+
+// Stores of a once-written output stream.  Write-through (sc1) buffer stores
+// beat nontemporal ones in tools/membench.hip's copy (C2 footprint: 83.4-83.9
+// vs 85.0-85.5 us) and write-only stream (43.6 vs 47.4 us), but NOT in
+// k_decode: 90.7 vs 87.9 us on C2 and 0.825 vs 0.782 ms on C3's ragged
+// frames, and 90.1 vs 86.3 us with buffer loads too (tools/tune.py, same box,
+// interleaved, two boxes), so decode keeps nontemporal stores; the fan-out
+// (write-only) takes them.  WSG_OUT_SC1=1 builds the decode variant for A/B.
+#ifndef WSG_OUT_SC1
+#define WSG_OUT_SC1 0
+#endif
+#ifndef WSG_OUT_AUX
+#define WSG_OUT_AUX 16   // cache-policy bits of the write-through stores (16 = sc1, 17 = sc0 | sc1; A/B)
+#endif
+struct OutTile {
+    uint8_t* p;   // tile base (wave-uniform)
+    bool sc1;
+    __amdgpu_buffer_rsrc_t rs;
+    __device__ __forceinline__ OutTile(uint8_t* base, uint32_t bytes, bool write_through = WSG_OUT_SC1 != 0)
+        : p(base), sc1(write_through)
+    {
+        if (sc1)
+            rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, bytes, 0x00020000);
+    }
+    // whole 16-B chunk at tile offset o (o + 16 <= bytes)
+    __device__ __forceinline__ void put(uint32_t o, v4u v) const
+    {
+        if (sc1)
+            __builtin_amdgcn_raw_buffer_store_b128(v, rs, o, 0, WSG_OUT_AUX);
+        else
+            st16nt(p + o, v);
+    }
+};
 
 // Byte j (runtime) of a 16-byte value, through two 64-bit halves so that no
 // register array is indexed at run time (that would spill to scratch).

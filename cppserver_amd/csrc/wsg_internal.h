@@ -1,5 +1,6 @@
 // wsg_internal.h — kernel geometry and kernel declarations shared by the
-// kernel sources (wsg_kernels.hip, wsg_messages.hip, wsg_frames.hip,
+// kernel sources (wsg_decode.hip, wsg_encode.hip, wsg_fanout.hip,
+// wsg_lane_device.hip, wsg_misc.hip, wsg_messages.hip, wsg_frames.hip,
 // wsg_utf8.hip, wsg_proto.hip, wsg_assembly.hip, wsg_upgrade.hip) and the C-ABI implementation (wsg_ctx.h).
 #pragma once
 
@@ -44,17 +45,14 @@ constexpr uint64_t SMALL_RANGE = WSG_SMALL_RANGE;        // ... wire bytes per b
 constexpr int SCAN_PER_LANE = WSG_SCAN_PER_LANE;   // encode scan: frames per lane
 constexpr uint64_t SCAN_ITEMS = uint64_t(BLOCK) * SCAN_PER_LANE;   // frames per scan block
 
-__global__ void k_decode(const uint8_t* wire, uint8_t* out, uint64_t wire_len, const uint64_t* fs, uint32_t n,
-                         double frames_per_byte, uint32_t stride, wsg_recv_info* info, unsigned long long* err,
-                         uint64_t num_tiles);
-__global__ void k_xor(const uint8_t* src, uint8_t* dst, uint64_t len, uint32_t key, uint32_t phase);
-
-// Host launchers, each defined next to its kernels: in wsg_kernels.hip unless
-// its section names another source.
-// One-launch decode (k_decode): grid blocks over the wire's tiles, per-frame
-// info and the error latch from the same launch.
+// Host launchers, each defined next to its kernels in the source its section names.
+// ---- one-launch decode (wsg_decode_batch; wsg_decode.hip) -------------------
+// k_decode: grid blocks over the wire's tiles, per-frame info and the error
+// latch from the same launch.
 hipError_t launch_decode(hipStream_t s, int grid, const uint8_t* wire, uint8_t* out, uint64_t wire_len,
                          const uint64_t* fs, uint32_t n, wsg_recv_info* info, unsigned long long* err);
+
+// ---- batch encode (wsg_encode_batch; wsg_encode.hip) ------------------------
 // Sizes + piece counts scan (scan: 4 * ceil(n / SCAN_ITEMS) words), wire
 // offsets, piece starts (n + 1 each) and the piece -> frame map.
 hipError_t launch_encode_scan(hipStream_t s, const wsg_send_desc* desc, uint32_t n, uint64_t* wire_off,
@@ -71,6 +69,7 @@ hipError_t launch_encode_scan_small(hipStream_t s, const wsg_send_desc* desc, ui
 hipError_t launch_encode_small(hipStream_t s, const uint8_t* payload, const wsg_send_desc* desc, uint32_t n,
                                uint64_t* wire_off, const uint64_t* scan, uint8_t* wire, uint64_t wire_cap,
                                unsigned long long* err);
+
 // ---- message assembly (wsg_decode_messages; wsg_messages.hip) ---------------
 // Plan scratch of one call, carved by the host out of one device block
 // (msg_plan_layout): per-frame scan results, per-block partials (one block =
@@ -378,7 +377,7 @@ hipError_t launch_proto_finish(hipStream_t s, int grid, uint32_t n, const uint32
                                const wsg_stream_state* state, wsg_proto_state* proto, const ProtoPlan& plan,
                                const wsg_proto_verdict* verdict, uint64_t* result);
 
-// ---- fan-out, XOR, offset rebase, test hook (wsg_kernels.hip) ---------------
+// ---- fan-out (wsg_fanout_encode, wsg_fanout_encode_many; wsg_fanout.hip) ----
 // Messages of one fan-out launch (blockIdx.y): payload and output offsets.
 constexpr int FAN_MSGS = 32;
 struct FanMsgs {
@@ -392,6 +391,8 @@ bool launch_fanout_period(hipStream_t s, int cus, int waves_per_cu, int wpb, con
                           uint8_t* wire, const FanMsgs& msgs, uint32_t nmsgs, hipError_t* err);
 hipError_t launch_fanout(hipStream_t s, int grid, const uint8_t* payload, uint64_t len, const uint32_t* keys,
                          uint32_t k, uint8_t opcode, uint32_t mask, uint64_t fsize, uint8_t* wire);
+
+// ---- single-buffer XOR, offset rebase, test hook (wsg_misc.hip) -------------
 hipError_t launch_xor(hipStream_t s, int grid, const uint8_t* src, uint8_t* dst, uint64_t len, uint32_t key,
                       uint32_t phase);
 // Multi-GPU gather (wsg_mgpu.cpp): the job's wire offsets from the ranks'
@@ -403,7 +404,8 @@ hipError_t launch_rebase_offsets(hipStream_t s, const uint64_t* stage, const uin
 // Test hook only: one wave waiting `us` microseconds (at most 0.2 s) on `s`.
 hipError_t launch_test_spin(hipStream_t s, uint32_t us);
 
-// ---- the host lane: one resident kernel per device for small host batches
+// ---- the host lane (wsg_lane_device.hip; host side: wsg_lane.cpp) -----------
+// One resident kernel per device for small host batches.
 // A host batch of a few KiB (an echo's read: ~1000 frames of 38 B) costs a
 // launch and a synchronize per pass (10 us for an empty kernel on MI355X,
 // tools/smallpass.hip) on top of its PCIe round trips.  The lane is launched

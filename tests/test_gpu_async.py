@@ -399,7 +399,7 @@ def _two_batches():
 
 
 def _pieces(desc):
-    """The piece kernel's count for these frames (pieces_of, wsg_kernels.hip)."""
+    """The piece kernel's count for these frames (pieces_of, wsg_encode.hip)."""
     return int(((ca.frame_sizes(desc) + np.uint64(127 + 4095)) // np.uint64(4096)).sum())
 
 

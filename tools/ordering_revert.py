@@ -55,8 +55,10 @@ def main():
     h = "/opt/rocm/bin/hipcc"
     inc = ["-I" + os.path.join(ROOT, "include"), "-I" + csrc]
     objs = []
-    for name in ("wsg_kernels.hip", "wsg_messages.hip", "wsg_frames.hip", "wsg_utf8.hip", "wsg_proto.hip", "wsg_assembly.hip", "wsg_capi.cpp", "wsg_lane.cpp", "wsg_capi_device.cpp",
-                 "wsg_capi_host.cpp", "wsg_proto_host.cpp", "ws.cpp", "ws_api.cpp", "ws_batch.cpp", "http.cpp", "tls.cpp",
+    for name in ("wsg_decode.hip", "wsg_encode.hip", "wsg_fanout.hip", "wsg_lane_device.hip", "wsg_misc.hip",
+                 "wsg_messages.hip", "wsg_frames.hip", "wsg_utf8.hip", "wsg_proto.hip", "wsg_assembly.hip",
+                 "wsg_upgrade.hip", "wsg_capi.cpp", "wsg_lane.cpp", "wsg_capi_device.cpp", "wsg_capi_host.cpp",
+                 "wsg_proto_host.cpp", "wsg_upgrade_host.cpp", "ws.cpp", "ws_api.cpp", "ws_batch.cpp", "http.cpp", "tls.cpp",
                  "wss.cpp", "wsg_mgpu.cpp"):
         src = os.path.join(TMP if name == "wsg_mgpu.cpp" else csrc, name)
         o = os.path.join(out, name + ".o")

@@ -1,5 +1,6 @@
 """Register/occupancy report for k_decode and source variants with paths cut
-out (which path sets the kernel's VGPR count), and for k_msg_gather
+out (which path sets the kernel's VGPR count), for the encode, lane, fan-out
+and XOR kernels, and for k_msg_gather
 (wsg_decode_messages; wsg_reply_messages runs it too), the reply plan, the
 framer, the UTF-8 check (dense and from the wire), the protocol check,
 the checked reply (wsg_reply_checked) and the upgrade handshake (wsg_upgrade_streams).  Compiles for gfx950 only (no GPU needed).
@@ -47,14 +48,19 @@ def cut(text, marker):
 
 
 if __name__ == "__main__":
-    src = source("wsg_kernels.hip")
+    src = source("wsg_decode.hip")
     staged = "    // staged: payload segments in LDS"
     boundary = "        // boundary: per chunk"
     report(src, "full")
     report(cut(src, staged), "no-staged")
     report(cut(src, boundary), "no-boundary")
     report(cut(cut(src, staged), boundary), "no-staged-no-boundary")
-    for name, kernels in (("wsg_messages.hip", ("k_msg_gather", "k_msg_finalize", "k_reply_local<0>", "k_reply_blocks<0>",
+    for name, kernels in (("wsg_encode.hip", ("k_encode_mask", "k_encode_small", "k_encode_finalize")),
+                          ("wsg_lane_device.hip", ("k_lane",)),
+                          ("wsg_fanout.hip", ("k_fanout_flat", "k_fanout_period<1>", "k_fanout_period<2>",
+                                              "k_fanout_period<4>")),
+                          ("wsg_misc.hip", ("k_xor",)),
+                          ("wsg_messages.hip", ("k_msg_gather", "k_msg_finalize", "k_reply_local<0>", "k_reply_blocks<0>",
                                                 "k_reply_finalize<0>", "k_msg_consumed", "k_reply_local<1>",
                                                 "k_reply_blocks<1>", "k_reply_finalize<1>")),
                           ("wsg_assembly.hip", ("k_rfc_scan_local", "k_rfc_scan_blocks", "k_rfc_bytes_local",
@@ -70,5 +76,6 @@ if __name__ == "__main__":
                                                "k_upgrade_accept", "k_upgrade_respond"))):
         src = source(name)
         for k in kernels:
-            base, _, flag = k.partition("<")   # name<0|1>: an instantiation of a template on one bool
-            report(src, k, kernel="_ZN3wsg%d%s" % (len(base), base) + ("ILb%sEE" % flag[0] if flag else ""))
+            base, _, flag = k.partition("<")   # name<0|1>: an instantiation of a template on one bool (the fan-out's: one int)
+            kind = "i" if base == "k_fanout_period" else "b"
+            report(src, k, kernel="_ZN3wsg%d%s" % (len(base), base) + ("IL%s%sEE" % (kind, flag[0]) if flag else ""))
