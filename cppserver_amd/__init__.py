@@ -24,6 +24,7 @@ from .layout import (  # noqa: F401  (re-exported)
     AHEAD_CAP, ASSEMBLY_REFERENCE, ASSEMBLY_RFC, message_frames,
     UP_ACCEPTED, UP_BAD_CONNECTION, UP_BAD_HTTP, UP_BAD_UPGRADE, UP_BAD_VERSION, UP_EMPTY_KEY, UP_INCOMPLETE,
     UP_MISSING, UP_NOT_GET, UP_NOT_WEBSOCKET, UP_TOO_LONG, UPGRADE_DTYPE, UPGRADE_RESP_MAX, upgrade_plan,
+    STREAM_READ, carry_plan,
 )
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -92,6 +93,7 @@ def lib(path=None):
         "wsg_check_protocol": (ci, [vp, vp, u64, vp, u32, vp, u32, vp, vp, u32, u64, vp, vp, vp]),
         "wsg_proto_judge": (ci, [vp, vp, vp, u32, u64, vp, ctypes.POINTER(ctypes.c_uint16)]),
         "wsg_upgrade_streams": (ci, [vp, vp, u64, vp, u32, u64, vp, vp, u64, vp, vp, vp]),
+        "wsg_carry_streams": (ci, [vp, vp, u64, vp, u32, vp, vp, u64, vp, vp, u64, vp, vp, vp]),
         "wsg_upgrade_judge": (ci, [vp, u64, u64, vp, vp, u32, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "wsg_encode_batch": (ci, [vp, vp, vp, u32, vp, u64, vp, vp]),
         "wsg_fanout_encode": (ci, [vp, vp, u64, vp, u32, ctypes.c_uint8, ci, vp, u64, vp]),
@@ -571,6 +573,52 @@ class Codec:
                                          self._stream(stream))
         _check(rc, "wsg_upgrade_streams")
         return up, resp, resp_off, count
+
+    def carry_streams(self, wire, spans, new, reads, close_off=None, next=None, next_cap=None, next_spans=None,
+                      count=None, stream=None):
+        """wsg_carry_streams: the next round's wire and span table from the
+        last round's ``wire`` and ``spans`` (uint8, n_streams * 32 bytes, as
+        that round's calls left them) and the bytes just read: ``new`` with
+        ``reads`` (uint8, n_streams * 16 bytes, STREAM_READ; None: no stream
+        has new bytes).  ``close_off`` (None, or n_streams words as
+        reply_checked / reply_validated write them) drops the streams whose
+        word is not 2**64 - 1.  ``wire`` and ``new`` may be None for no bytes.
+        Returns (next, next_spans, count): the wire (``next_cap`` bytes of
+        room; default what always suffices), its STREAM_SPAN records and count
+        int64[4] = [bytes of next, tail bytes, new bytes, streams dropped].  A
+        total above ``next_cap`` latches WSG_ENOMEM (sync) with no byte of
+        ``next`` written."""
+        t = self._torch
+        ns = int(spans.numel()) // STREAM_SPAN.itemsize
+        if spans.element_size() != 1 or int(spans.numel()) != ns * STREAM_SPAN.itemsize:
+            raise WSGError(WSG_EINVAL, "carry_streams: spans must be uint8, n_streams * 32 bytes")
+        dev = spans.device
+        wire_len = 0 if wire is None else int(wire.numel())
+        new_len = 0 if new is None else int(new.numel())
+        if next_cap is None:   # a stream adds less than 16 bytes of padding to its bytes
+            next_cap = wire_len + new_len + 16 * ns if next is None else int(next.numel())
+        cap = int(next_cap)
+        if next is None:
+            next = t.empty(max(cap, 16), dtype=t.uint8, device=dev)
+        if next_spans is None:
+            next_spans = t.empty(max(ns, 1) * STREAM_SPAN.itemsize, dtype=t.uint8, device=dev)
+        if count is None:
+            count = t.empty(4, dtype=t.int64, device=dev)
+        if (cap > int(next.numel()) or next.element_size() != 1
+                or int(next_spans.numel()) * next_spans.element_size() < ns * STREAM_SPAN.itemsize
+                or (reads is not None and int(reads.numel()) * reads.element_size() < ns * STREAM_READ.itemsize)
+                or (close_off is not None and (close_off.element_size() != 8 or int(close_off.numel()) < ns))
+                or count.element_size() != 8 or int(count.numel()) < 4):
+            raise WSGError(WSG_EINVAL, "carry_streams: a buffer is smaller than the batch needs")
+
+        def ptr(x):
+            return ctypes.c_void_p(None if x is None else x.data_ptr())
+
+        rc = self._L.wsg_carry_streams(self._ctx, ptr(wire), wire_len, ptr(spans), ns, ptr(close_off), ptr(new),
+                                       new_len, ptr(reads), ptr(next), cap, ptr(next_spans), ptr(count),
+                                       self._stream(stream))
+        _check(rc, "wsg_carry_streams")
+        return next, next_spans, count
 
     def decode_streams(self, wire, spans, state=None, frame_start=None, frame_cap=None, stream_first=None,
                        msg=None, msg_cap=None, stream=None, msgs=None, count=None, info=None):

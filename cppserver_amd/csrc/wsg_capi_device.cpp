@@ -332,6 +332,55 @@ int wsg_upgrade_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, ws
     return scratch_leave(c->frame_order, s, ordered);
 }
 
+// The carry: per-stream sizes and a scan (one lane per stream), then the copy,
+// which writes every 16-byte chunk of the next wire once.  The framer's
+// scratch and its order: a round is one call or the other at a time.
+int wsg_carry_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const wsg_stream_span* d_span,
+                      uint32_t n_streams, const uint64_t* d_close_off, const uint8_t* d_new, uint64_t new_len,
+                      const wsg_stream_read* d_read, uint8_t* d_next, uint64_t next_cap, wsg_stream_span* d_next_span,
+                      uint64_t* d_count, void* stream)
+{
+    if (!c || !d_count || (wire_len && !d_wire) || (new_len && !d_new) || (next_cap && !d_next) ||
+        (n_streams && (!d_span || !d_next_span)) || n_streams == UINT32_MAX)
+        return WSG_EINVAL;
+    if (!aligned16(d_wire) || !aligned16(d_new) || !aligned16(d_next) || !aligned8(d_span) || !aligned8(d_close_off) ||
+        !aligned8(d_read) || !aligned8(d_next_span) || !aligned8(d_count))
+        return WSG_EINVAL;
+    const auto overlap = [](const uint8_t* a, uint64_t an, const uint8_t* b, uint64_t bn) {
+        return an && bn && a < b + bn && b < a + an;
+    };
+    if ((n_streams && d_next_span == d_span) || overlap(d_next, next_cap, d_wire, wire_len) ||
+        overlap(d_next, next_cap, d_new, new_len))
+        return WSG_EINVAL;
+    if (c->check &&
+        (!in_alloc(d_wire, (wire_len + 15) & ~uint64_t(15)) || !in_alloc(d_new, (new_len + 15) & ~uint64_t(15)) ||
+         !in_alloc(d_next, next_cap) || !in_alloc(d_span, uint64_t(n_streams) * sizeof(wsg_stream_span)) ||
+         (d_close_off && !in_alloc(d_close_off, uint64_t(n_streams) * 8)) ||
+         (d_read && !in_alloc(d_read, uint64_t(n_streams) * sizeof(wsg_stream_read))) ||
+         !in_alloc(d_next_span, uint64_t(n_streams) * sizeof(wsg_stream_span)) || !in_alloc(d_count, 4 * 8)))
+        return WSG_EINVAL;
+    hipStream_t s = as_stream(stream);
+    if (int rc = ensure_array(c->d_frame_plan, c->frame_plan_cap, wsg::carry_plan_layout(nullptr, n_streams, nullptr)))
+        return rc;
+    wsg::CarryPlan plan;
+    wsg::carry_plan_layout(c->d_frame_plan, n_streams, &plan);
+    bool ordered = false;
+    if (int rc = scratch_enter(c->frame_order, s, &ordered))
+        return rc;
+    WSG_HIP(wsg::launch_carry_plan(s, wire_len, d_span, n_streams, d_close_off, new_len, d_read, next_cap, d_next_span,
+                                   d_count, plan, c->d_err));
+    // the pieces the copy can have: a stream adds less than a chunk of padding
+    // to its bytes, and a total above next_cap writes nothing
+    const uint64_t most = std::min(next_cap, wire_len + new_len + uint64_t(n_streams) * wsg::CHUNK);
+    if (n_streams && most) {
+        const int t = timing_begin(c, s);
+        WSG_HIP(wsg::launch_carry_copy(s, grid_for(c, ceil_div(ceil_div(most, wsg::PIECE), wsg::BLOCK / 64), c->dec_blocks_per_cu),
+                                       d_wire, d_new, n_streams, plan, d_next, next_cap));
+        timing_end(c, s, t);
+    }
+    return scratch_leave(c->frame_order, s, ordered);
+}
+
 namespace {
 
 // wsg_decode_streams and wsg_reply_streams: the framer, one synchronisation

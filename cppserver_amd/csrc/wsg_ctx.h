@@ -89,8 +89,9 @@ struct wsg_ctx {
     wsg::MsgPiece* d_msg_pieces = nullptr;
     uint64_t msg_pieces_cap = 0;
     wsg_scratch_order msg_order;   // wsg_decode_messages calls
-    // wsg_frame_streams: per-stream counts and scan partials (wsg::frame_plan_layout); wsg_upgrade_streams: its plan
-    // (wsg::upgrade_plan_layout) in the same array, under the same order
+    // wsg_frame_streams: per-stream counts and scan partials (wsg::frame_plan_layout); wsg_upgrade_streams and
+    // wsg_carry_streams: their plans (wsg::upgrade_plan_layout, wsg::carry_plan_layout) in the same array, under the
+    // same order
     uint64_t* d_frame_plan = nullptr;
     uint64_t frame_plan_cap = 0;
     wsg_scratch_order frame_order;   // wsg_frame_streams calls

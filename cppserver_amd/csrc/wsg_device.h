@@ -1,6 +1,6 @@
 // wsg_device.h — device helpers shared by the kernel sources (wsg_decode.hip,
 // wsg_encode.hip, wsg_fanout.hip, wsg_lane_device.hip, wsg_misc.hip,
-// wsg_messages.hip, wsg_frames.hip, wsg_utf8.hip, wsg_proto.hip, wsg_assembly.hip, wsg_upgrade.hip): 16-byte loads
+// wsg_messages.hip, wsg_frames.hip, wsg_utf8.hip, wsg_proto.hip, wsg_assembly.hip, wsg_upgrade.hip, wsg_carry.hip): 16-byte loads
 // and stores, byte funnels and shifts, the output tile, the frame parse, the block scan, the wave
 // reductions, the stream search, a _streams call's span, the error latch and the wsg_msg record codec.  Internal linkage: every source gets its own copy.
 #pragma once
@@ -175,6 +175,30 @@ __device__ __forceinline__ SpanIn span_in(const wsg_stream_span* span, uint32_t 
             ok = false;
     }
     s.ok = uni(uint32_t(ok)) != 0;
+    return s;
+}
+
+// Span j as span_in judges it, for a lane of its own (span_in's values are
+// the wave's): off, len, consumed and whether the span may be walked.
+struct SpanLane {
+    uint64_t off, len, consumed;
+    bool ok;
+};
+
+__device__ __forceinline__ SpanLane span_in_lane(const wsg_stream_span* span, uint64_t j, uint64_t wire_len)
+{
+    const uint64_t* w = reinterpret_cast<const uint64_t*>(span + j);
+    SpanLane s;
+    s.off = w[0];
+    s.len = w[1];
+    s.consumed = w[2];
+    s.ok = s.off <= wire_len && s.len <= wire_len - s.off;
+    if (s.ok && j > 0) {
+        const uint64_t* p = reinterpret_cast<const uint64_t*>(span + (j - 1));
+        const uint64_t poff = p[0], plen = p[1];
+        if (poff <= wire_len && plen <= wire_len - poff && s.off < poff + plen)
+            s.ok = false;
+    }
     return s;
 }
 
@@ -426,6 +450,39 @@ __device__ __forceinline__ uint32_t stream_of(const uint32_t* __restrict__ sf, u
             lo = mid;
         else
             hi = mid;
+    }
+    return lo;
+}
+
+// Last j in [lo, hi) with off[j] <= p (lo when there is none): stream_of over
+// 64-bit offsets and a range of streams (an empty stream shares its offset
+// with the next one, which wins).
+__device__ __forceinline__ uint32_t stream_of64(const uint64_t* __restrict__ off, uint32_t lo, uint32_t hi, uint64_t p)
+{
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (off[mid] <= p)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+// stream_of64 by the whole wave, every argument and the result wave-uniform
+// (off[lo] <= p): lane i probes the i-th of 64 evenly spaced entries and a
+// ballot picks the interval, so 4096 streams take two dependent loads and
+// 2^18 three, where the binary search takes twelve and eighteen.
+__device__ __forceinline__ uint32_t stream_of64_wave(const uint64_t* __restrict__ off, uint32_t lo, uint32_t hi,
+                                                     uint64_t p, uint32_t lane)
+{
+    while (hi - lo > 1) {
+        const uint32_t step = (hi - lo + 63) / 64;
+        const uint64_t at = uint64_t(lo) + uint64_t(lane) * step;
+        const bool le = at < hi && off[at] <= p;   // true in lanes 0..k-1: off does not decrease
+        const uint32_t k = max(uint32_t(__builtin_popcountll(__ballot(le))), 1u);
+        lo = uni(lo + (k - 1) * step);
+        hi = min(lo + step, hi);
     }
     return lo;
 }

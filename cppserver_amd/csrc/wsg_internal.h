@@ -1,7 +1,7 @@
 // wsg_internal.h — kernel geometry and kernel declarations shared by the
 // kernel sources (wsg_decode.hip, wsg_encode.hip, wsg_fanout.hip,
 // wsg_lane_device.hip, wsg_misc.hip, wsg_messages.hip, wsg_frames.hip,
-// wsg_utf8.hip, wsg_proto.hip, wsg_assembly.hip, wsg_upgrade.hip) and the C-ABI implementation (wsg_ctx.h).
+// wsg_utf8.hip, wsg_proto.hip, wsg_assembly.hip, wsg_upgrade.hip, wsg_carry.hip) and the C-ABI implementation (wsg_ctx.h).
 #pragma once
 
 #include "wsg_frame.h"
@@ -288,6 +288,30 @@ hipError_t launch_upgrade_streams(hipStream_t s, int grid, const uint8_t* wire, 
                                   wsg_stream_span* span, uint32_t ns, uint64_t max_request, wsg_upgrade* up,
                                   uint8_t* resp, uint64_t resp_cap, uint64_t* resp_off, uint64_t* count,
                                   const UpgradePlan& plan, unsigned long long* err);
+
+// ---- the carry between two rounds (wsg_carry_streams; wsg_carry.hip) --------
+// Scratch of one call, carved out of the framer's device array (one block =
+// BLOCK streams).
+struct CarryPlan {
+    uint64_t* tsrc;    // ns: wire offset of the stream's tail
+    uint64_t* tlen;    // ns: its bytes
+    uint64_t* nsrc;    // ns: offset in d_new of the stream's read
+    uint64_t* nlen;    // ns: its bytes
+    uint64_t* ex;      // ns: block-local exclusive prefix of the streams' padded sizes
+    uint64_t* off;     // ns + 1: the streams' offsets in d_next; [ns] its bytes used
+    uint64_t* bsum;    // 4 * nb: block sums of padded sizes, tail bytes, read bytes, dropped streams
+    uint64_t* bpre;    // nb: exclusive prefixes of the first of those
+};
+uint64_t carry_plan_layout(uint64_t* base, uint32_t ns, CarryPlan* plan);
+// Sizes, scan, offsets: next_span (ns), count (4), the plan's runs; latches
+// the streams' errors and the capacity.
+hipError_t launch_carry_plan(hipStream_t s, uint64_t wire_len, const wsg_stream_span* span, uint32_t ns,
+                             const uint64_t* close_off, uint64_t new_len, const wsg_stream_read* read, uint64_t next_cap,
+                             wsg_stream_span* next_span, uint64_t* count, const CarryPlan& plan, unsigned long long* err);
+// k_carry_copy (ns > 0): every chunk of next below the plan's total, when that
+// fits next_cap; grid blocks of four waves, a PIECE per wave and pass.
+hipError_t launch_carry_copy(hipStream_t s, int grid, const uint8_t* wire, const uint8_t* fresh, uint32_t ns,
+                             const CarryPlan& plan, uint8_t* next, uint64_t next_cap);
 
 // ---- UTF-8 on the device (wsg_check_utf8; wsg_utf8.hip) ---------------------
 // k_utf8_init: d_valid[m] = len for m < min(d_count[0], msg_room), and

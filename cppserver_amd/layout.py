@@ -841,3 +841,63 @@ def upgrade_plan(wire, spans, max_request=0):
     count = np.array([np.sum(up["code"] == UP_ACCEPTED), np.sum(up["status"] == 400),
                       np.sum(up["code"] == UP_INCOMPLETE), resp_off[ns]], dtype=np.uint64)
     return up, consumed, need, resp_off, np.frombuffer(b"".join(resp), dtype=np.uint8), count, bad
+
+
+# wsg_stream_read: where a stream's new bytes lie in a wsg_carry_streams call's d_new.
+STREAM_READ = np.dtype([("off", "<u8"), ("len", "<u8")])
+
+assert STREAM_READ.itemsize == 16
+
+
+def carry_plan(wire, spans, new, reads, close_off=None, next_cap=None):
+    """wsg_carry_streams restated on the host, from its contract: the next
+    round's wire is, per stream, the tail ``wire[off + consumed, off + len)``
+    followed by the read ``new[read.off, read.off + read.len)``.
+
+    ``spans``: STREAM_SPAN records as the last round's calls left them;
+    ``reads``: STREAM_READ records or None (no stream has new bytes);
+    ``close_off``: None, or per stream a word that drops the stream unless it
+    is 2**64 - 1.  Returns (next, next_spans, count, key): the bytes of
+    d_next[0, count[0]), every stream at the next multiple of 16 behind the
+    one before it and the padding zero; the STREAM_SPAN records {off, len,
+    0, 0}; count = [bytes of next, tail bytes, new bytes, streams dropped];
+    and the latch's key, None when nothing is latched: the smallest of
+    stream << 8 | 22 over the streams refused (a span bad_spans refuses,
+    consumed > len, or, on a stream not dropped, a read past the end of
+    ``new``; such a stream is empty) and, given ``next_cap``, n_streams << 8
+    | 12 when count[0] exceeds it (the call then writes no byte of d_next)."""
+    wire = np.asarray(wire, dtype=np.uint8)
+    new = np.asarray(new, dtype=np.uint8)
+    spans = np.asarray(spans, dtype=STREAM_SPAN)
+    ns = len(spans)
+    bad = bad_spans(len(wire), spans)
+    out = np.zeros(ns, dtype=STREAM_SPAN)
+    parts, at, tails, news, dropped, key = [], 0, 0, 0, 0, None
+    for j in range(ns):
+        off, length, used = (int(spans[f][j]) for f in ("off", "len", "consumed"))
+        drop = close_off is not None and int(close_off[j]) != U64_MAX
+        dropped += drop
+        refused = bool(bad[j]) or used > length
+        tail = fresh = b""
+        if not refused and not drop:
+            tail = wire[off + used: off + length].tobytes()
+            if reads is not None:
+                r_off, r_len = int(reads["off"][j]), int(reads["len"][j])
+                if r_off + r_len > len(new):
+                    refused = True
+                else:
+                    fresh = new[r_off: r_off + r_len].tobytes()
+        if refused:
+            tail = fresh = b""
+            if key is None:
+                key = j << 8 | -WSG_EINVAL
+        size = len(tail) + len(fresh)
+        out["off"][j], out["len"][j] = at, size
+        parts += [tail, fresh, bytes(-size % 16)]
+        at += size + -size % 16
+        tails += len(tail)
+        news += len(fresh)
+    if key is None and next_cap is not None and at > next_cap:
+        key = ns << 8 | -WSG_ENOMEM
+    count = np.array([at, tails, news, dropped], dtype=np.uint64)
+    return np.frombuffer(b"".join(parts), dtype=np.uint8), out, count, key

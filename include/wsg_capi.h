@@ -880,6 +880,63 @@ int wsg_reply_validated_streams(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wi
                                 wsg_msg* d_msgs, uint64_t* d_count, wsg_recv_info* d_info,
                                 uint32_t* n_frames_out, void* stream);
 
+/* ---- the carry: the next round's wire built on the device ------------------ */
+/* (Added without an ABI bump: one struct and one symbol.)
+ *
+ * Every _streams call returns d_span[j].consumed and leaves the rest of the
+ * stream, a partial frame and the fragments of a message whose FIN frame has
+ * not arrived, to be submitted again in front of the connection's next bytes.
+ * wsg_carry_streams does that on the device: the last round's wire and span
+ * table stay where they are, the host uploads only what it has just read, and
+ * one asynchronous call writes the next round's wire and span table.
+ *
+ * Stream j of the next round is stream j of this one, for every j: no index is
+ * compacted, a dropped or finished connection is an empty stream, and the
+ * d_state / d_proto tables stay in place from round to round.  Its bytes are
+ * tail || new: tail = d_wire[off + consumed, off + len) of d_span[j], new =
+ * d_new[off, off + len) of d_read[j] (d_read NULL: no stream has new bytes).
+ * d_close_off: NULL, or n_streams words as wsg_reply_checked* /
+ * wsg_reply_validated* write them; any value other than UINT64_MAX drops
+ * stream j, both parts empty and d_read[j] not looked at.
+ *
+ * d_next: the streams in index order, stream 0 at 0, each at the next multiple
+ * of 16 behind the one before it; the padding up to that multiple, behind the
+ * last stream too, is written as 0, so every byte of d_next[0, d_count[0]) is
+ * defined, d_count[0] is a multiple of 16, and no byte from d_count[0] on is
+ * written.  d_next_span[j] = {off, len = tail + new, consumed 0, need 0} for
+ * every j (a dropped stream: len 0, off where it would lie).  d_count[0..4):
+ * the bytes of d_next used (the next wire_len), the tail bytes carried, the
+ * new bytes taken, the streams dropped.
+ *
+ * Latched for wsg_sync as wsg_frame_streams latches: WSG_EINVAL under stream
+ * << 8 | code for a span wsg_frame_streams would refuse, consumed > len, or,
+ * on a stream that is not dropped, a read that runs past new_len; that stream
+ * is empty in d_next and the others are unaffected.  WSG_ENOMEM under
+ * n_streams << 8 | code when d_count[0] > next_cap: no byte of d_next is
+ * written, d_next_span and d_count are final.
+ *
+ * d_wire, d_new and d_next 16-byte aligned, the sources readable and d_next
+ * writable to the end of their last 16-byte block, the tables 8-byte aligned;
+ * d_next overlaps neither source and d_next_span is not d_span.  d_wire may be
+ * NULL when wire_len is 0, d_new when new_len is 0, d_next when next_cap is 0.
+ * n_streams == 0 and a first round over a zeroed span table are valid.
+ * WSG_EINVAL for a NULL or misaligned operand or an overlap.  Asynchronous on
+ * `stream`, no host synchronisation.  The call uses wsg_frame_streams'
+ * scratch of the ctx and is ordered across streams with those calls, under
+ * the same capture rule: run it once uncaptured with the same n_streams
+ * before capturing.                                                          */
+typedef struct wsg_stream_read {
+    uint64_t off;   /* stream j's new bytes are d_new[off, off + len) */
+    uint64_t len;
+} wsg_stream_read;      /* 16 bytes */
+
+int wsg_carry_streams(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
+                      const wsg_stream_span* d_span, uint32_t n_streams,
+                      const uint64_t* d_close_off /* or NULL */,
+                      const uint8_t* d_new, uint64_t new_len, const wsg_stream_read* d_read /* or NULL */,
+                      uint8_t* d_next, uint64_t next_cap, wsg_stream_span* d_next_span,
+                      uint64_t* d_count /* 4 */, void* stream);
+
 /* ---- batch encode: header pack + mask (PrepareSendFrame over many frames) */
 /* Frames are written back to back into d_wire (16-byte aligned, capacity
  * wire_cap bytes).  d_wire_off[0..n] receives each frame's offset;

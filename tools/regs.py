@@ -3,7 +3,8 @@ out (which path sets the kernel's VGPR count), for the encode, lane, fan-out
 and XOR kernels, and for k_msg_gather
 (wsg_decode_messages; wsg_reply_messages runs it too), the reply plan, the
 framer, the UTF-8 check (dense and from the wire), the protocol check,
-the checked reply (wsg_reply_checked) and the upgrade handshake (wsg_upgrade_streams).  Compiles for gfx950 only (no GPU needed).
+the checked reply (wsg_reply_checked), the upgrade handshake (wsg_upgrade_streams) and the carry
+(wsg_carry_streams).  Compiles for gfx950 only (no GPU needed).
 
 usage: python tools/regs.py
 """
@@ -73,7 +74,8 @@ if __name__ == "__main__":
                           ("wsg_proto.hip", ("k_proto_local", "k_proto_blocks", "k_proto_judge", "k_proto_finish",
                                              "k_proto_merge")),
                           ("wsg_upgrade.hip", ("k_upgrade_parse", "k_upgrade_scan_local", "k_upgrade_scan_blocks",
-                                               "k_upgrade_accept", "k_upgrade_respond"))):
+                                               "k_upgrade_accept", "k_upgrade_respond")),
+                          ("wsg_carry.hip", ("k_carry_sizes", "k_carry_scan_blocks", "k_carry_spans", "k_carry_copy"))):
         src = source(name)
         for k in kernels:
             base, _, flag = k.partition("<")   # name<0|1>: an instantiation of a template on one bool (the fan-out's: one int)
