@@ -25,6 +25,7 @@ from .layout import (  # noqa: F401  (re-exported)
     UP_ACCEPTED, UP_BAD_CONNECTION, UP_BAD_HTTP, UP_BAD_UPGRADE, UP_BAD_VERSION, UP_EMPTY_KEY, UP_INCOMPLETE,
     UP_MISSING, UP_NOT_GET, UP_NOT_WEBSOCKET, UP_TOO_LONG, UPGRADE_DTYPE, UPGRADE_RESP_MAX, upgrade_plan,
     STREAM_READ, carry_plan,
+    CHAT_RELAY, CHAT_REPLY, relay_plan, relay_tables_bad,
 )
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -86,6 +87,11 @@ def lib(path=None):
                                      vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "wsg_reply_validated_streams": (ci, [vp, vp, u64, vp, u32, vp, vp, u32, vp, vp, u32, u64, u32, vp, ci, vp, vp,
                                              u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(u32), vp]),
+        "wsg_relay_validated": (ci, [vp, vp, u64, vp, u32, vp, u32, vp, vp, u32, u64, vp, u32, vp, ci, vp, vp, vp, vp,
+                                     u32, vp, u64, vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "wsg_relay_validated_streams": (ci, [vp, vp, u64, vp, u32, vp, vp, u32, vp, vp, u32, u64, u32, vp, ci, vp, vp,
+                                             vp, vp, u32, vp, u64, vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp,
+                                             vp, vp, ctypes.POINTER(u32), vp]),
         "wsg_utf8_verdicts": (ci, [vp, vp, vp, u32, u32, vp, u32, vp, vp]),
         "wsg_check_utf8_wire": (ci, [vp, vp, u64, vp, u32, vp, u32, vp, u32, vp, vp, vp, vp, vp, vp]),
         "wsg_check_utf8": (ci, [vp, vp, u64, vp, vp, u32, u32, vp, vp, vp]),
@@ -917,6 +923,122 @@ class Codec:
         _check(rc, "wsg_reply_validated_streams")
         return (reply, reply_off, stream_reply, close_off, verdict, proto, result, msgs, count, state, info, valid,
                 utf8_result, frame_start, stream_first, n.value)
+
+    # -- relays (reply_validated with a chat server's rooms behind it) -----------
+    def _relay_args(self, what, wire, n, ns, relay_op, order, group_first, relay, relay_cap, relay_off, group_relay,
+                    count):
+        t = self._torch
+        dev = wire.device
+        rule = bytes(int(x) for x in relay_op)
+        if len(rule) != 5:
+            raise WSGError(WSG_EINVAL, "%s: relay_op must hold five bytes (indexed by CB_*)" % what)
+        if order is not None and (order.element_size() != 4 or int(order.numel()) < ns):
+            raise WSGError(WSG_EINVAL, "%s: order must hold n_streams 32-bit indices" % what)
+        if group_first is not None and (group_first.element_size() != 4 or int(group_first.numel()) < 1):
+            raise WSGError(WSG_EINVAL, "%s: group_first must hold n_groups + 1 32-bit positions" % what)
+        ng = int(group_first.numel()) - 1 if group_first is not None else 1
+        if relay_cap is None:   # as reply_cap: wire bytes + 14 * n always suffices
+            relay_cap = int(wire.numel()) + 14 * n if relay is None else int(relay.numel())
+        cap = int(relay_cap)
+        if relay is None:
+            relay = t.empty(max(cap, 16), dtype=t.uint8, device=dev)
+        if relay_off is None:
+            relay_off = t.empty(max(n, 1), dtype=t.int64, device=dev)
+        if group_relay is None:
+            group_relay = t.empty(ng + 1, dtype=t.int64, device=dev)
+        if count is None:
+            count = t.empty(8, dtype=t.int64, device=dev)
+        if (cap > int(relay.numel()) or int(relay_off.numel()) < n or relay_off.element_size() != 8
+                or int(group_relay.numel()) < ng + 1 or group_relay.element_size() != 8
+                or int(count.numel()) < 8 or count.element_size() != 8):
+            raise WSGError(WSG_EINVAL, "%s: a buffer is smaller than the batch needs" % what)
+        return rule, ng, cap, relay, relay_off, group_relay, count
+
+    def relay_validated(self, wire, frame_start, stream_first, proto=None, role=PROTO_ANY, max_message=0, also=None,
+                        which=UTF8_TEXT | UTF8_CLOSE, reply_op=CHAT_REPLY, mask=False, send_keys=None,
+                        relay_op=CHAT_RELAY, order=None, group_first=None, state=None, reply=None, reply_cap=None,
+                        relay=None, relay_cap=None, stream=None, reply_off=None, stream_reply=None, close_off=None,
+                        relay_off=None, group_relay=None, verdict=None, result=None, valid=None, utf8_result=None,
+                        msgs=None, count=None, info=None):
+        """wsg_relay_validated: reply_validated, and the messages whose kind
+        ``relay_op`` names (five bytes by CB_*, as reply_op; a kind is replied
+        to or relayed, not both) written once as unmasked server frames into
+        ``relay``, one range per room.  ``order``: int32 CUDA tensor, a
+        permutation of the stream indices (None: the identity);
+        ``group_first``: int32 CUDA tensor of n_groups + 1 positions (None: one
+        room of everyone).  Returns reply_validated's tuple, its count int64[8]
+        = [.., relay bytes, relay frames, 0], followed by (relay, relay_off,
+        group_relay): int64[n] frame starts per message (-1: not relayed;
+        count[0] valid) and int64[n_groups + 1] offsets per room.
+        ``relay_cap`` defaults to wire bytes + 14 * n, which always suffices."""
+        n = int(frame_start.numel())
+        ns = int(stream_first.numel()) - 1
+        if ns < 0 or stream_first.element_size() != 4:
+            raise WSGError(WSG_EINVAL, "relay_validated: stream_first must hold n_streams + 1 32-bit indices")
+        rrule, ng, rcap, relay, relay_off, group_relay, count = self._relay_args(
+            "relay_validated", wire, n, ns, relay_op, order, group_first, relay, relay_cap, relay_off, group_relay,
+            count)
+        proto, close_off, verdict, result, count = self._checked_args("relay_validated", wire.device, ns, proto,
+                                                                      close_off, verdict, result, count)
+        if also is not None and int(also.numel()) * also.element_size() < ns * PROTO_VERDICT.itemsize:
+            raise WSGError(WSG_EINVAL, "relay_validated: also must hold n_streams verdicts")
+        valid, utf8_result = self._validated_args("relay_validated", wire.device, n, valid, utf8_result)
+        rule, cap, reply, reply_off, stream_reply, state, msgs, count, info = self._reply_args(
+            "relay_validated", wire, n, ns, reply_op, send_keys, reply, reply_cap, reply_off, stream_reply, state,
+            msgs, count, info)
+        p = ctypes.c_void_p
+        rc = self._L.wsg_relay_validated(
+            self._ctx, p(wire.data_ptr()), wire.numel(), p(frame_start.data_ptr()), n, p(stream_first.data_ptr()), ns,
+            p(state.data_ptr()), p(proto.data_ptr()), int(role), int(max_message),
+            p(also.data_ptr()) if also is not None else None, int(which), rule, 1 if mask else 0,
+            p(send_keys.data_ptr()) if send_keys is not None else None, rrule,
+            p(order.data_ptr()) if order is not None else None,
+            p(group_first.data_ptr()) if group_first is not None else None, ng, p(reply.data_ptr()), cap,
+            p(reply_off.data_ptr()), p(stream_reply.data_ptr()), p(close_off.data_ptr()), p(relay.data_ptr()), rcap,
+            p(relay_off.data_ptr()), p(group_relay.data_ptr()), p(verdict.data_ptr()), p(result.data_ptr()),
+            p(valid.data_ptr()), p(utf8_result.data_ptr()), p(msgs.data_ptr()), p(count.data_ptr()),
+            p(info.data_ptr()), self._stream(stream))
+        _check(rc, "wsg_relay_validated")
+        return (reply, reply_off, stream_reply, close_off, verdict, proto, result, msgs, count, state, info, valid,
+                utf8_result, relay, relay_off, group_relay)
+
+    def relay_validated_streams(self, wire, spans, proto=None, role=PROTO_ANY, max_message=0,
+                                which=UTF8_TEXT | UTF8_CLOSE, reply_op=CHAT_REPLY, mask=False, send_keys=None,
+                                relay_op=CHAT_RELAY, order=None, group_first=None, state=None, frame_start=None,
+                                frame_cap=None, stream_first=None, reply=None, reply_cap=None, relay=None,
+                                relay_cap=None, stream=None, reply_off=None, stream_reply=None, close_off=None,
+                                relay_off=None, group_relay=None, verdict=None, result=None, valid=None,
+                                utf8_result=None, msgs=None, count=None, info=None):
+        """wsg_relay_validated_streams: reply_validated_streams with
+        relay_validated in the middle.  Returns relay_validated's tuple
+        followed by (frame_start, stream_first, n_frames)."""
+        ns, fcap, frame_start, stream_first = self._frame_args("relay_validated_streams", wire, spans, frame_start,
+                                                               frame_cap, stream_first)
+        rrule, ng, rcap, relay, relay_off, group_relay, count = self._relay_args(
+            "relay_validated_streams", wire, fcap, ns, relay_op, order, group_first, relay, relay_cap, relay_off,
+            group_relay, count)
+        proto, close_off, verdict, result, count = self._checked_args("relay_validated_streams", wire.device, ns,
+                                                                      proto, close_off, verdict, result, count)
+        valid, utf8_result = self._validated_args("relay_validated_streams", wire.device, fcap, valid, utf8_result)
+        rule, cap, reply, reply_off, stream_reply, state, msgs, count, info = self._reply_args(
+            "relay_validated_streams", wire, fcap, ns, reply_op, send_keys, reply, reply_cap, reply_off, stream_reply,
+            state, msgs, count, info)
+        n = ctypes.c_uint32()
+        p = ctypes.c_void_p
+        rc = self._L.wsg_relay_validated_streams(
+            self._ctx, p(wire.data_ptr()), wire.numel(), p(spans.data_ptr()), ns, p(state.data_ptr()),
+            p(frame_start.data_ptr()), fcap, p(stream_first.data_ptr()), p(proto.data_ptr()), int(role),
+            int(max_message), int(which), rule, 1 if mask else 0,
+            p(send_keys.data_ptr()) if send_keys is not None else None, rrule,
+            p(order.data_ptr()) if order is not None else None,
+            p(group_first.data_ptr()) if group_first is not None else None, ng, p(reply.data_ptr()), cap,
+            p(reply_off.data_ptr()), p(stream_reply.data_ptr()), p(close_off.data_ptr()), p(relay.data_ptr()), rcap,
+            p(relay_off.data_ptr()), p(group_relay.data_ptr()), p(verdict.data_ptr()), p(result.data_ptr()),
+            p(valid.data_ptr()), p(utf8_result.data_ptr()), p(msgs.data_ptr()), p(count.data_ptr()),
+            p(info.data_ptr()), ctypes.byref(n), self._stream(stream))
+        _check(rc, "wsg_relay_validated_streams")
+        return (reply, reply_off, stream_reply, close_off, verdict, proto, result, msgs, count, state, info, valid,
+                utf8_result, relay, relay_off, group_relay, frame_start, stream_first, n.value)
 
     def utf8_verdicts(self, msgs, count, valid, n_streams, which=UTF8_TEXT | UTF8_CLOSE, msg_room=None, also=None,
                       stream=None):

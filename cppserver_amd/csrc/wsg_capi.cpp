@@ -219,6 +219,8 @@ int wsg_destroy(wsg_ctx* c)
     (void)hipFree(c->d_frame_plan);
     (void)hipFree(c->d_msg_plan);
     (void)hipFree(c->d_msg_pieces);
+    (void)hipFree(c->d_relay_plan);
+    (void)hipFree(c->d_relay_pieces);
     (void)hipFree(c->d_stage);
     if (c->h_stage)
         (void)hipHostFree(c->h_stage);

@@ -103,6 +103,33 @@ int gather_launch(wsg_ctx* c, hipStream_t s, decltype(wsg::launch_msg_gather)* l
     return WSG_OK;
 }
 
+// What wsg_relay_validated adds to wsg_reply_validated's arguments.
+struct RelayArgs {
+    const uint8_t* relay_op;
+    const uint32_t* d_order;
+    const uint32_t* d_group_first;
+    uint32_t n_groups;
+    uint8_t* d_relay;
+    uint64_t relay_cap;
+    uint64_t* d_relay_off;
+    uint64_t* d_group_relay;
+};
+
+// Its scratch for n frames in n_streams streams: the plan block and piece
+// records of its own (the reply's gather reads the message plan's while the
+// relay's are written), the context's, under the message plan's order, which
+// the caller has entered.
+int relay_scratch(wsg_ctx* c, uint32_t n, uint32_t n_streams, uint64_t pieces_cap, wsg::RelayPlan* plan)
+{
+    const uint64_t block = wsg::relay_plan_layout(nullptr, n, n_streams, nullptr);
+    if (int rc = ensure_array(c->d_relay_plan, c->relay_plan_cap, block))
+        return rc;
+    if (int rc = ensure_array(c->d_relay_pieces, c->relay_pieces_cap, pieces_cap))
+        return rc;
+    wsg::relay_plan_layout(c->d_relay_plan, n, n_streams, plan);
+    return WSG_OK;
+}
+
 } // namespace
 
 int wsg_decode_batch(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const uint64_t* d_frame_start, uint32_t n,
@@ -514,8 +541,29 @@ int reply_checked(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const ui
                   uint64_t reply_cap, uint64_t* d_reply_off, uint64_t* d_stream_reply, uint64_t* d_close_off,
                   wsg_proto_verdict* d_verdict, uint64_t* d_result, wsg_msg* d_msgs, uint64_t* d_count,
                   wsg_recv_info* d_info, void* stream, bool validated, uint32_t which, uint64_t* d_valid,
-                  uint64_t* d_utf8_result)
+                  uint64_t* d_utf8_result, const RelayArgs* relay = nullptr)
 {
+    bool relays = false;   // a kind is relayed: the relay's gather has something to move
+    if (relay) {
+        const RelayArgs& r = *relay;
+        if (!r.relay_op || !reply_op || !r.d_group_relay || (r.relay_cap && !r.d_relay) || (n && !r.d_relay_off) ||
+            (!r.d_group_first && r.n_groups != 1) || (r.n_groups == 0 && n_streams != 0) || r.n_groups == UINT32_MAX)
+            return WSG_EINVAL;
+        for (int k = 0; k < 5; ++k) {
+            if (r.relay_op[k] && reply_op[k])
+                return WSG_EINVAL;   // a kind is replied to or relayed, not both
+            relays = relays || (k >= 1 && r.relay_op[k]);
+        }
+        if (!aligned16(r.d_relay) || !aligned8(r.d_relay_off) || !aligned8(r.d_group_relay) ||
+            (reinterpret_cast<uintptr_t>(r.d_order) & 3u) || (reinterpret_cast<uintptr_t>(r.d_group_first) & 3u))
+            return WSG_EINVAL;
+        if (c && c->check &&
+            (!in_alloc(r.d_relay, r.relay_cap) || !in_alloc(r.d_relay_off, uint64_t(n) * 8) ||
+             !in_alloc(r.d_group_relay, (uint64_t(r.n_groups) + 1) * 8) || !in_alloc(d_count, 8 * 8) ||
+             (r.d_order && !in_alloc(r.d_order, uint64_t(n_streams) * 4)) ||
+             (r.d_group_first && !in_alloc(r.d_group_first, (uint64_t(r.n_groups) + 1) * 4))))
+            return WSG_EINVAL;
+    }
     if (validated) {
         if (!d_utf8_result || (n && !d_valid) || !aligned8(d_valid) || !aligned8(d_utf8_result))
             return WSG_EINVAL;
@@ -559,6 +607,10 @@ int reply_checked(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const ui
         return rc;
     if (int rc = msg_scratch(c, s, n, wire_len, &plan, &pieces_cap, &ordered))
         return rc;
+    wsg::RelayPlan rplan;
+    if (relay)
+        if (int rc = relay_scratch(c, n, n_streams, pieces_cap, &rplan))
+            return rc;
     utf8.rec_grid = grid_for(c, ceil_div(n, wsg::BLOCK));
     utf8.wire_grid = utf8_wire_grid(c, pieces_cap);
     WSG_HIP(wsg::launch_reply_checked_plan(s, grid_for(c, ceil_div(n_streams, wsg::BLOCK)), d_wire, wire_len,
@@ -570,6 +622,21 @@ int reply_checked(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const ui
     if (n)
         if (int rc = gather_launch(c, s, wsg::launch_reply_gather, d_wire, plan.ref, pieces_cap, d_reply, reply_cap))
             return rc;
+    if (relay) {
+        // behind the whole reply side, which it reads (d_info, d_msgs, d_verdict) and leaves as it is
+        wsg::ReplyRule rrule = make_rule(relay->relay_op, 0);
+        WSG_HIP(wsg::launch_relay_plan(s, d_info, n, n_streams, d_msgs, d_verdict, plan, rrule, relay->d_order,
+                                       relay->d_group_first, relay->n_groups, relay->d_relay, relay->relay_cap,
+                                       relay->d_relay_off, relay->d_group_relay, d_count, rplan, c->d_relay_pieces,
+                                       pieces_cap, c->d_err));
+        if (n && relays) {
+            const int t = timing_begin(c, s);
+            WSG_HIP(wsg::launch_relay_gather(s, grid_for(c, ceil_div(pieces_cap, wsg::BLOCK / 64), c->enc_blocks_per_cu),
+                                             d_wire, rplan, c->d_relay_pieces, pieces_cap, relay->d_relay,
+                                             relay->relay_cap));
+            timing_end(c, s, t);
+        }
+    }
     if (int rc = scratch_leave(c->proto_order, s, pordered))
         return rc;
     return scratch_leave(c->msg_order, s, ordered);
@@ -664,6 +731,67 @@ int wsg_reply_validated_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire
                                                        reply_op, mask, d_send_key, d_reply, reply_cap, d_reply_off,
                                                        d_stream_reply, d_close_off, d_verdict, d_result, d_valid,
                                                        d_utf8_result, d_msgs, d_count, d_info, stream);
+                        });
+}
+
+// wsg_reply_validated with the relay's plan and gather behind it: the reply
+// side runs as it does there, then every relayed message is sized, placed by
+// room and moved once into d_relay.
+int wsg_relay_validated(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const uint64_t* d_frame_start,
+                        uint32_t n, const uint32_t* d_stream_first, uint32_t n_streams, wsg_stream_state* d_state,
+                        wsg_proto_state* d_proto, uint32_t role, uint64_t max_message, const wsg_proto_verdict* d_also,
+                        uint32_t which, const uint8_t reply_op[5], int mask, const uint32_t* d_send_key,
+                        const uint8_t relay_op[5], const uint32_t* d_order, const uint32_t* d_group_first,
+                        uint32_t n_groups, uint8_t* d_reply, uint64_t reply_cap, uint64_t* d_reply_off,
+                        uint64_t* d_stream_reply, uint64_t* d_close_off, uint8_t* d_relay, uint64_t relay_cap,
+                        uint64_t* d_relay_off, uint64_t* d_group_relay, wsg_proto_verdict* d_verdict,
+                        uint64_t* d_result, uint64_t* d_valid, uint64_t* d_utf8_result, wsg_msg* d_msgs,
+                        uint64_t* d_count, wsg_recv_info* d_info, void* stream)
+{
+    const RelayArgs relay{relay_op, d_order, d_group_first, n_groups, d_relay, relay_cap, d_relay_off, d_group_relay};
+    return reply_checked(c, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams, d_state, d_proto, role,
+                         max_message, d_also, reply_op, mask, d_send_key, d_reply, reply_cap, d_reply_off,
+                         d_stream_reply, d_close_off, d_verdict, d_result, d_msgs, d_count, d_info, stream, true, which,
+                         d_valid, d_utf8_result, &relay);
+}
+
+int wsg_relay_validated_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_stream_span* d_span,
+                                uint32_t n_streams, wsg_stream_state* d_state, uint64_t* d_frame_start,
+                                uint32_t frame_cap, uint32_t* d_stream_first, wsg_proto_state* d_proto, uint32_t role,
+                                uint64_t max_message, uint32_t which, const uint8_t reply_op[5], int mask,
+                                const uint32_t* d_send_key, const uint8_t relay_op[5], const uint32_t* d_order,
+                                const uint32_t* d_group_first, uint32_t n_groups, uint8_t* d_reply,
+                                uint64_t reply_cap, uint64_t* d_reply_off, uint64_t* d_stream_reply,
+                                uint64_t* d_close_off, uint8_t* d_relay, uint64_t relay_cap, uint64_t* d_relay_off,
+                                uint64_t* d_group_relay, wsg_proto_verdict* d_verdict, uint64_t* d_result,
+                                uint64_t* d_valid, uint64_t* d_utf8_result, wsg_msg* d_msgs, uint64_t* d_count,
+                                wsg_recv_info* d_info, uint32_t* n_frames_out, void* stream)
+{
+    if (!c || !n_frames_out || !d_count || !reply_op || !relay_op || !d_reply_off || !d_stream_reply || !d_close_off ||
+        !d_proto || !d_verdict || !d_result || !d_utf8_result || !d_group_relay || (n_streams && !d_state) ||
+        (reply_cap && !d_reply) || (relay_cap && !d_relay) ||
+        (frame_cap && (!d_msgs || !d_info || !d_valid || !d_relay_off)) || !aligned16(d_reply) ||
+        !aligned16(d_relay) || role > WSG_PROTO_CLIENT)
+        return WSG_EINVAL;
+    for (int k = 0; k < 5; ++k)
+        if (relay_op[k] && reply_op[k])
+            return WSG_EINVAL;
+    if (c->check &&
+        (!in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) || !in_alloc(d_reply, reply_cap) ||
+         !in_alloc(d_reply_off, (uint64_t(frame_cap) + 1) * 8) ||
+         !in_alloc(d_msgs, uint64_t(frame_cap) * sizeof(wsg_msg)) || !in_alloc(d_valid, uint64_t(frame_cap) * 8) ||
+         !in_alloc(d_relay_off, uint64_t(frame_cap) * 8) ||
+         !in_alloc(d_info, uint64_t(frame_cap) * sizeof(wsg_recv_info))))
+        return WSG_EINVAL;
+    return streams_then(c, d_wire, wire_len, d_span, n_streams, d_state, d_frame_start, frame_cap, d_stream_first,
+                        d_count, n_frames_out, stream, [&](uint32_t n) {
+                            return wsg_relay_validated(c, d_wire, wire_len, d_frame_start, n, d_stream_first,
+                                                       n_streams, d_state, d_proto, role, max_message, nullptr, which,
+                                                       reply_op, mask, d_send_key, relay_op, d_order, d_group_first,
+                                                       n_groups, d_reply, reply_cap, d_reply_off, d_stream_reply,
+                                                       d_close_off, d_relay, relay_cap, d_relay_off, d_group_relay,
+                                                       d_verdict, d_result, d_valid, d_utf8_result, d_msgs, d_count,
+                                                       d_info, stream);
                         });
 }
 

@@ -88,6 +88,11 @@ struct wsg_ctx {
     uint64_t msg_plan_cap = 0;
     wsg::MsgPiece* d_msg_pieces = nullptr;
     uint64_t msg_pieces_cap = 0;
+    // wsg_relay_validated: its plan block (wsg::relay_plan_layout) and the piece records of its gather, under msg_order
+    uint8_t* d_relay_plan = nullptr;
+    uint64_t relay_plan_cap = 0;
+    wsg::MsgPiece* d_relay_pieces = nullptr;
+    uint64_t relay_pieces_cap = 0;
     wsg_scratch_order msg_order;   // wsg_decode_messages calls
     // wsg_frame_streams: per-stream counts and scan partials (wsg::frame_plan_layout); wsg_upgrade_streams and
     // wsg_carry_streams: their plans (wsg::upgrade_plan_layout, wsg::carry_plan_layout) in the same array, under the

@@ -1,6 +1,6 @@
 // wsg_device.h — device helpers shared by the kernel sources (wsg_decode.hip,
 // wsg_encode.hip, wsg_fanout.hip, wsg_lane_device.hip, wsg_misc.hip,
-// wsg_messages.hip, wsg_frames.hip, wsg_utf8.hip, wsg_proto.hip, wsg_assembly.hip, wsg_upgrade.hip, wsg_carry.hip): 16-byte loads
+// wsg_messages.hip, wsg_frames.hip, wsg_utf8.hip, wsg_proto.hip, wsg_assembly.hip, wsg_upgrade.hip, wsg_carry.hip, wsg_relay.hip): 16-byte loads
 // and stores, byte funnels and shifts, the output tile, the frame parse, the block scan, the wave
 // reductions, the stream search, a _streams call's span, the error latch and the wsg_msg record codec.  Internal linkage: every source gets its own copy.
 #pragma once

@@ -1,7 +1,7 @@
 // wsg_internal.h — kernel geometry and kernel declarations shared by the
 // kernel sources (wsg_decode.hip, wsg_encode.hip, wsg_fanout.hip,
 // wsg_lane_device.hip, wsg_misc.hip, wsg_messages.hip, wsg_frames.hip,
-// wsg_utf8.hip, wsg_proto.hip, wsg_assembly.hip, wsg_upgrade.hip, wsg_carry.hip) and the C-ABI implementation (wsg_ctx.h).
+// wsg_utf8.hip, wsg_proto.hip, wsg_assembly.hip, wsg_upgrade.hip, wsg_carry.hip, wsg_relay.hip) and the C-ABI implementation (wsg_ctx.h).
 #pragma once
 
 #include "wsg_frame.h"
@@ -217,6 +217,55 @@ hipError_t launch_reply_checked_plan(hipStream_t s, int stream_grid, const uint8
 // k_msg_gather over those records: every replied payload byte, re-keyed, to its place in reply.
 hipError_t launch_reply_gather(hipStream_t s, int grid, const uint8_t* wire, const MsgPlan& plan,
                                const MsgPiece* pieces, uint64_t pieces_cap, uint8_t* reply, uint64_t reply_cap);
+
+// ---- relays (wsg_relay_validated; wsg_relay.hip) -----------------------------
+// Scratch of one call, carved by the host out of one device block
+// (relay_plan_layout; one block = BLOCK messages, frames or positions).
+struct RelayPlan {
+    // per message m (the first d_count[0] of n), block-local
+    uint64_t* mex;      // n: relay bytes of the messages before m
+    // per frame i, block-local but fmsg
+    uint64_t* fex;      // n: data bytes of the relayed frames before i (under WSG_ASSEMBLY_RFC: of data frames)
+    uint32_t* fpc;      // n: pieces of the relayed frames before i
+    uint32_t* fmsg;     // n: the relayed message whose data frame i holds (UINT32_MAX: none)
+    // per position p, block-local
+    uint64_t* pex;      // ns: relay bytes of the streams at the positions before p
+    // per stream j
+    uint32_t* mfirst;   // ns: its first message and one past its last (both 0: none)
+    uint32_t* mend;
+    uint32_t* inv;      // ns: the lowest position that names j (UINT32_MAX: none)
+    // block partials and their exclusive prefixes
+    uint64_t* bm;       // nb: relay bytes
+    uint64_t* bm_pre;
+    uint64_t* bn;       // nb: relay frames
+    uint64_t* bw;       // nb: data bytes
+    uint64_t* bw_pre;
+    uint64_t* bp;       // nb: pieces
+    uint64_t* bp_pre;
+    uint64_t* bs;       // nbs: relay bytes by position
+    uint64_t* bs_pre;
+    uint64_t* tot;      // [0] relay bytes, [1] relay frames, [2] pieces, whatever the tables hold
+    uint64_t* gtot;     // [0] the tables keep their rules; as the gather reads it: [2] relay bytes, [3] pieces
+    uint64_t* bad;      // the lowest offending position (n_streams + g: entry g of d_group_first); UINT64_MAX: none
+};
+// Bytes of that block for n frames in ns streams; plan (or null) gets the pointers into base.
+uint64_t relay_plan_layout(uint8_t* base, uint32_t n, uint32_t ns, RelayPlan* plan);
+// Behind launch_reply_checked_plan (d_info, d_msgs, d_verdict and plans.ref.tot
+// final): d_relay_off, d_group_relay, d_count[5..8), every relay frame's header
+// and status prefix and the piece records of the relayed frames, whose
+// destination is d_relay and whose key is the receive key; latches WSG_EINVAL
+// (order, group_first; index n + 1 + the plan's `bad`) and WSG_ENOMEM
+// (relay_cap; index n + 1).  A relay frame is unmasked: the launcher clears rule.mask, whatever the
+// caller's rule holds, before the kernels size a frame with it.
+hipError_t launch_relay_plan(hipStream_t s, const wsg_recv_info* info, uint32_t n, uint32_t n_streams,
+                             const wsg_msg* msgs, const wsg_proto_verdict* verdict, const MsgPlans& plans,
+                             const ReplyRule& rule, const uint32_t* order, const uint32_t* group_first,
+                             uint32_t n_groups, uint8_t* relay, uint64_t relay_cap, uint64_t* relay_off,
+                             uint64_t* group_relay, uint64_t* count, const RelayPlan& Q, MsgPiece* pieces,
+                             uint64_t pieces_cap, unsigned long long* err);
+// k_msg_gather over those records: every relayed payload byte, unmasked, to its place in relay.
+hipError_t launch_relay_gather(hipStream_t s, int grid, const uint8_t* wire, const RelayPlan& Q,
+                               const MsgPiece* pieces, uint64_t pieces_cap, uint8_t* relay, uint64_t relay_cap);
 
 // ---- WSG_ASSEMBLY_RFC (wsg_set_assembly; wsg_assembly.hip) ------------------
 // The plan kernels of RFC 6455 5.4's rule, in the places the launchers of

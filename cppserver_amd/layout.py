@@ -686,6 +686,79 @@ def checked_reply_plan(msgs, verdict, reply_op, mask, send_keys=None, n_streams=
     return reply_off, stream_reply, close_off, count
 
 
+# ---- relays (wsg_relay_validated) ---------------------------------------------
+# The reference's chat server (examples/ws_chat_server.cpp:35-46): every text
+# message goes to every session, a ping is answered to its sender.
+CHAT_REPLY = (0, 0, 0, WS_FIN | WS_PONG, 0)
+CHAT_RELAY = (0, WS_FIN | WS_TEXT, 0, 0, 0)
+
+
+def relay_tables_bad(n_streams, order=None, group_first=None):
+    """The lowest offending position of wsg_relay_validated's room tables, or
+    None when they keep their rules: a position p whose ``order`` entry is
+    >= n_streams or names a stream that a lower position names; behind every
+    position, n_streams + g for an entry g of ``group_first`` that is not 0 at
+    g == 0, lies below entry g - 1, or is not n_streams at the last entry."""
+    if order is not None:
+        seen = set()
+        for p, j in enumerate(np.asarray(order).tolist()[:n_streams]):
+            if j >= n_streams or j in seen:
+                return p
+            seen.add(j)
+    if group_first is not None:
+        gf = np.asarray(group_first).tolist()
+        for g, v in enumerate(gf):
+            if (g == 0 and v != 0) or (g > 0 and v < gf[g - 1]) or (g == len(gf) - 1 and v != n_streams):
+                return n_streams + g
+    return None
+
+
+def relay_plan(msgs, verdict, relay_op, order=None, group_first=None):
+    """The sizes and offsets of wsg_relay_validated's relay side (not its bytes).
+
+    ``msgs``: a message_plan table; ``verdict``: the effective PROTO_VERDICT
+    per stream (n_streams of them); ``relay_op``: five bytes indexed by CB_*
+    (entry 0 ignored), with reply_op's meaning; ``order``: a permutation of
+    the stream indices, None the identity; ``group_first``: n_groups + 1
+    positions, None one room of everyone.  A message is relayed when
+    relay_op names its kind and the frame that ends it lies in front of its
+    stream's terminal frame; its frame is unmasked.  Returns (relay_off,
+    group_relay, count): per message the start of its relay frame in d_relay
+    or 2**64 - 1, n_groups + 1 offsets (group g's range, the last the total),
+    count = [relay bytes, relay frames, 0].  When the tables break their rules
+    (relay_tables_bad) nothing is relayed: all 2**64 - 1, all 0, [0, 0, 0]."""
+    msgs = np.asarray(msgs, dtype=MSG)
+    verdict = np.asarray(verdict, dtype=PROTO_VERDICT)
+    ns = len(verdict)
+    n_groups = 1 if group_first is None else len(group_first) - 1
+    relay_off = np.full(len(msgs), U64_MAX, dtype=np.uint64)
+    if relay_tables_bad(ns, order, group_first) is not None:
+        return relay_off, np.zeros(n_groups + 1, dtype=np.uint64), np.zeros(3, dtype=np.uint64)
+    sizes = np.diff(reply_plan(msgs, relay_op, False, n_streams=ns)[0].astype(np.int64))
+    last = msgs["first_frame"].astype(np.int64) + msgs["nframes"].astype(np.int64) - 1
+    has = _verdict_words(verdict) != U64_MAX if ns else np.zeros(0, dtype=bool)
+    term = np.where(has, verdict["frame"].astype(np.int64), np.int64(2**62))
+    if len(msgs):
+        sizes = np.where(last < term[msgs["stream"]], sizes, 0)
+    per_stream = np.zeros(ns, dtype=np.int64)
+    if len(msgs):
+        np.add.at(per_stream, msgs["stream"].astype(np.int64), sizes)
+    order = np.arange(ns, dtype=np.int64) if order is None else np.asarray(order).astype(np.int64)
+    # the bytes in front of position p, and of the stream that stands there
+    before_pos = np.concatenate([[0], np.cumsum(per_stream[order])]).astype(np.int64)
+    base = np.zeros(ns, dtype=np.int64)
+    base[order] = before_pos[:-1]
+    if len(msgs):   # messages are stream-major: a stream's relayed messages follow its base back to back
+        before = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        stream = msgs["stream"].astype(np.int64)
+        first = np.searchsorted(stream, np.arange(ns))
+        at = base[stream] + before[:-1] - before[np.minimum(first, len(msgs))[stream]]
+        relay_off = np.where(sizes > 0, at, -1).astype(np.int64).view(np.uint64)
+    gf = np.array([0, ns], dtype=np.int64) if group_first is None else np.asarray(group_first).astype(np.int64)
+    count = np.array([int(before_pos[-1]), int((sizes > 0).sum()), 0], dtype=np.uint64)
+    return relay_off, before_pos[gf].astype(np.uint64), count
+
+
 # ---- the upgrade handshake (wsg_upgrade_streams) -----------------------------
 UPGRADE_DTYPE = np.dtype([("key_off", "<u8"), ("url_off", "<u8"), ("key_len", "<u4"), ("url_len", "<u4"),
                           ("resp_len", "<u4"), ("status", "<u2"), ("code", "u1"), ("_pad", "u1")])

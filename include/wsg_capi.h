@@ -937,6 +937,134 @@ int wsg_carry_streams(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
                       uint8_t* d_next, uint64_t next_cap, wsg_stream_span* d_next_span,
                       uint64_t* d_count /* 4 */, void* stream);
 
+/* ---- relays: a chat server's round, one buffer per room ---------------------- */
+/* (Added without an ABI bump: symbols only.)
+ *
+ * The reference's other server, ws_chat_server / ws_multicast_server, sends
+ * every received message to every session (WSServer::MulticastText,
+ * ws_server.h:50).  A server's frames are unmasked, so every recipient gets
+ * the same bytes: wsg_relay_validated writes a round's received messages,
+ * checked and validated as wsg_reply_validated does, once, as unmasked server
+ * frames, into one range of d_relay per room.
+ *
+ * The reply side is wsg_reply_validated's, byte for byte.  d_reply,
+ * d_reply_off, d_stream_reply, d_close_off, d_verdict, d_result, d_valid,
+ * d_utf8_result, d_msgs, d_info, d_state, d_proto, d_count[0..5) and the
+ * latches are what wsg_reply_validated writes for the same arguments; the
+ * terminal-frame rule, the close frames and both WSG_ASSEMBLY_* modes are
+ * unchanged.  mask and d_send_key belong to the reply side only.
+ * relay_op: five bytes indexed by WSG_CB_*, with reply_op's meaning: 0 none,
+ * WSG_REPLY_SAME relays under the message's own opcode, any other value is
+ * the whole first header byte.  A kind is replied to or relayed, not both:
+ * relay_op[k] and reply_op[k] both non-zero is WSG_EINVAL at once (every
+ * payload byte is read once for the check, once for the move, written once).
+ * With relay_op all zero the call is wsg_reply_validated: d_relay is
+ * untouched, d_count[5..8) are 0, every d_relay_off[m] is UINT64_MAX and
+ * every d_group_relay entry 0.  The reference's chat server is
+ *   reply_op = {0, 0, 0, WSG_FIN | WSG_PONG, 0}
+ *   relay_op = {0, WSG_FIN | WSG_TEXT, 0, 0, 0}
+ * A conformant server relays with WSG_REPLY_SAME: a binary message sent on as
+ * text has not been validated under WSG_UTF8_TEXT.
+ * Which messages.  Message m of stream j is relayed when relay_op[kind] is
+ * non-zero and the frame that ends the message lies in front of the stream's
+ * terminal frame (the rule by which wsg_reply_checked answers).  So an
+ * invalid text message is never relayed (its FIN frame is the terminal
+ * frame), nor anything of a failed stream behind its failure.
+ * The relay frame is what MulticastText / MulticastBinary leave in the
+ * server's _ws_send_buffer: PrepareSendFrame(op, false, data, size) with
+ * _ws_send_mask 0; for a close-kind message PrepareSendFrame(op, false, NULL,
+ * 0, status); the two-byte prefix on control opcodes as wsg_reply_messages
+ * writes it.
+ * Rooms.  d_order (n_streams 32-bit words, or NULL: the identity) is a
+ * permutation of the stream indices; group g is the streams d_order[p] for p
+ * in [d_group_first[g], d_group_first[g+1]).  d_group_first (n_groups + 1
+ * 32-bit words) starts at 0, ends at n_streams and does not decrease; empty
+ * groups are allowed.  d_group_first NULL needs n_groups == 1 and means one
+ * room of everyone; n_groups == 0 needs n_streams == 0 (both WSG_EINVAL at
+ * once otherwise).
+ * Layout.  d_relay (16-byte aligned, overlapping no other operand) holds the
+ * relay frames back to back with no padding, ordered by position p and,
+ * within a stream, by message.
+ *   d_group_relay[0..n_groups]  group g's bytes, which the host sends to every
+ *                               member of g, are the one range
+ *                               d_relay[d_group_relay[g], d_group_relay[g+1]);
+ *                               [n_groups] is the total
+ *   d_relay_off[0..d_count[0])  the start of message m's relay frame,
+ *                               UINT64_MAX when m is not relayed; nothing
+ *                               behind d_count[0] is written
+ *   d_count[5..8)               relay bytes, relay frames, 0
+ * wire_len + 14 * n always suffices for relay_cap.
+ * Errors, latched for wsg_sync behind every frame error (and behind the reply
+ * side's WSG_ENOMEM):
+ *   WSG_EINVAL  d_order is not a permutation or d_group_first breaks its
+ *               rule, keyed by the lowest offending position: a position p
+ *               whose entry is >= n_streams or names a stream that a lower
+ *               position names; behind every position, an entry g of
+ *               d_group_first that is not 0 at g == 0, is below entry g - 1,
+ *               or is not n_streams at g == n_groups.  Then no byte of
+ *               d_relay is written, d_count[5..8) are 0, every d_relay_off is
+ *               UINT64_MAX and every d_group_relay 0; the whole reply side is
+ *               final and unaffected.
+ *   WSG_ENOMEM  d_count[5] > relay_cap: no byte of d_relay is written and
+ *               every table is final.
+ * The two capacities are independent: a short reply_cap does not stop the
+ * relay, nor the reverse.
+ * Arguments: checked as wsg_reply_validated's; in addition WSG_EINVAL for
+ * NULL relay_op, NULL d_relay with relay_cap > 0, NULL d_relay_off with
+ * n > 0, NULL d_group_relay, d_relay not 16-byte aligned, d_relay_off or
+ * d_group_relay not 8-byte aligned, d_order or d_group_first not 4-byte
+ * aligned.
+ * Streams, capture, timing: as wsg_reply_validated (both scratches, both
+ * orders; the relay's plan and piece records live beside the message plan's,
+ * under its order); run it once uncaptured with the same n, n_streams and
+ * n_groups before capturing.  The timing hook brackets each of the two
+ * gathers, the reply's and the relay's: a call counts as two launches (one
+ * when relay_op is all zero, none when n == 0: a gather that has nothing to
+ * move is not launched).
+ * Send order.  To connection j the host sends its group's relay range first,
+ * then d_reply[d_stream_reply[j], d_stream_reply[j+1]): a stream's close frame
+ * is the last thing in that range, and no data frame may follow a close.     */
+int wsg_relay_validated(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
+                        const uint64_t* d_frame_start, uint32_t n,
+                        const uint32_t* d_stream_first, uint32_t n_streams,
+                        wsg_stream_state* d_state,
+                        wsg_proto_state* d_proto, uint32_t role, uint64_t max_message,
+                        const wsg_proto_verdict* d_also /* or NULL */, uint32_t which,
+                        const uint8_t reply_op[5], int mask, const uint32_t* d_send_key,
+                        const uint8_t relay_op[5],
+                        const uint32_t* d_order /* n_streams, or NULL */,
+                        const uint32_t* d_group_first /* n_groups + 1, or NULL */, uint32_t n_groups,
+                        uint8_t* d_reply, uint64_t reply_cap,
+                        uint64_t* d_reply_off, uint64_t* d_stream_reply, uint64_t* d_close_off,
+                        uint8_t* d_relay, uint64_t relay_cap,
+                        uint64_t* d_relay_off /* n words */, uint64_t* d_group_relay /* n_groups + 1 words */,
+                        wsg_proto_verdict* d_verdict, uint64_t* d_result,
+                        uint64_t* d_valid /* n words */, uint64_t* d_utf8_result /* 4 words */,
+                        wsg_msg* d_msgs, uint64_t* d_count /* 8 words */,
+                        wsg_recv_info* d_info, void* stream);
+
+/* Raw bytes to a chat round: wsg_reply_validated_streams with
+ * wsg_relay_validated (d_also NULL) in the place of wsg_reply_validated; the
+ * same returns, the same lowering of d_span[j].consumed and the same refusal
+ * while capturing; d_relay_off has room for frame_cap words.  A chat server's
+ * loop is one upload, wsg_carry_streams, this call and one wsg_sync.         */
+int wsg_relay_validated_streams(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
+                                wsg_stream_span* d_span, uint32_t n_streams, wsg_stream_state* d_state,
+                                uint64_t* d_frame_start, uint32_t frame_cap, uint32_t* d_stream_first,
+                                wsg_proto_state* d_proto, uint32_t role, uint64_t max_message,
+                                uint32_t which,
+                                const uint8_t reply_op[5], int mask, const uint32_t* d_send_key,
+                                const uint8_t relay_op[5],
+                                const uint32_t* d_order, const uint32_t* d_group_first, uint32_t n_groups,
+                                uint8_t* d_reply, uint64_t reply_cap,
+                                uint64_t* d_reply_off, uint64_t* d_stream_reply, uint64_t* d_close_off,
+                                uint8_t* d_relay, uint64_t relay_cap,
+                                uint64_t* d_relay_off, uint64_t* d_group_relay,
+                                wsg_proto_verdict* d_verdict, uint64_t* d_result,
+                                uint64_t* d_valid, uint64_t* d_utf8_result,
+                                wsg_msg* d_msgs, uint64_t* d_count, wsg_recv_info* d_info,
+                                uint32_t* n_frames_out, void* stream);
+
 /* ---- batch encode: header pack + mask (PrepareSendFrame over many frames) */
 /* Frames are written back to back into d_wire (16-byte aligned, capacity
  * wire_cap bytes).  d_wire_off[0..n] receives each frame's offset;

@@ -3,8 +3,8 @@ out (which path sets the kernel's VGPR count), for the encode, lane, fan-out
 and XOR kernels, and for k_msg_gather
 (wsg_decode_messages; wsg_reply_messages runs it too), the reply plan, the
 framer, the UTF-8 check (dense and from the wire), the protocol check,
-the checked reply (wsg_reply_checked), the upgrade handshake (wsg_upgrade_streams) and the carry
-(wsg_carry_streams).  Compiles for gfx950 only (no GPU needed).
+the checked reply (wsg_reply_checked), the upgrade handshake (wsg_upgrade_streams), the carry
+(wsg_carry_streams) and the relay plan (wsg_relay_validated).  Compiles for gfx950 only (no GPU needed).
 
 usage: python tools/regs.py
 """
@@ -75,7 +75,9 @@ if __name__ == "__main__":
                                              "k_proto_merge")),
                           ("wsg_upgrade.hip", ("k_upgrade_parse", "k_upgrade_scan_local", "k_upgrade_scan_blocks",
                                                "k_upgrade_accept", "k_upgrade_respond")),
-                          ("wsg_carry.hip", ("k_carry_sizes", "k_carry_scan_blocks", "k_carry_spans", "k_carry_copy"))):
+                          ("wsg_carry.hip", ("k_carry_sizes", "k_carry_scan_blocks", "k_carry_spans", "k_carry_copy")),
+                          ("wsg_relay.hip", ("k_relay_local", "k_relay_frames<0>", "k_relay_frames<1>", "k_relay_blocks",
+                                             "k_relay_streams_local", "k_relay_streams_blocks", "k_relay_finalize"))):
         src = source(name)
         for k in kernels:
             base, _, flag = k.partition("<")   # name<0|1>: an instantiation of a template on one bool (the fan-out's: one int)
