@@ -538,24 +538,24 @@ uint64_t rfc_plan_layout(uint8_t* base, uint32_t n, RfcPlan* plan)
     return c.at;
 }
 
-hipError_t launch_rfc_scans(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
-                            const uint32_t* stream_first, uint32_t n_streams, const wsg_stream_state* state,
-                            uint64_t msg_cap, uint64_t* count, wsg_recv_info* info, const MsgPlan& P, const RfcPlan& R,
-                            unsigned long long* err)
+hipError_t launch_rfc_scans(hipStream_t s, const Batch& b, const wsg_stream_state* state, uint64_t msg_cap,
+                            const MsgOut& o, const MsgScratch& x)
 {
-    const uint32_t nb = uint32_t((uint64_t(n) + BLOCK - 1) / BLOCK);
-    k_rfc_scan_local<<<nb, BLOCK, 0, s>>>(wire, wire_len, fs, n, stream_first, n_streams, info, P.sidx, R, err);
+    const MsgPlan& P = x.plans.ref;
+    const RfcPlan& R = x.plans.rfc;
+    const uint32_t nb = uint32_t((uint64_t(b.n) + BLOCK - 1) / BLOCK);
+    k_rfc_scan_local<<<nb, BLOCK, 0, s>>>(b.wire, b.wire_len, b.fs, b.n, b.stream_first, b.n_streams, o.info, P.sidx, R,
+                                          x.err);
     k_rfc_scan_blocks<<<1, BLOCK, 0, s>>>(R, nb);
-    k_rfc_bytes_local<<<nb, BLOCK, 0, s>>>(info, n, state, P.sidx, R);
-    k_rfc_bytes_blocks<<<1, BLOCK, 0, s>>>(P.tot, R, nb, n, msg_cap, count, err);
+    k_rfc_bytes_local<<<nb, BLOCK, 0, s>>>(o.info, b.n, state, P.sidx, R);
+    k_rfc_bytes_blocks<<<1, BLOCK, 0, s>>>(P.tot, R, nb, b.n, msg_cap, o.count, x.err);
     return hipGetLastError();
 }
 
-hipError_t launch_rfc_finalize(hipStream_t s, const uint8_t* wire, const wsg_recv_info* info, uint32_t n,
-                               const MsgPlan& P, const RfcPlan& R, wsg_msg* msgs, MsgPiece* pieces,
-                               uint64_t pieces_cap)
+hipError_t launch_rfc_finalize(hipStream_t s, const Batch& b, const MsgOut& o, const MsgScratch& x)
 {
-    k_rfc_finalize<<<uint32_t((uint64_t(n) + BLOCK - 1) / BLOCK), BLOCK, 0, s>>>(wire, info, n, P.sidx, R, msgs, pieces, pieces_cap);
+    k_rfc_finalize<<<uint32_t((uint64_t(b.n) + BLOCK - 1) / BLOCK), BLOCK, 0, s>>>(
+        b.wire, o.info, b.n, x.plans.ref.sidx, x.plans.rfc, o.msgs, x.pieces, x.pieces_cap);
     return hipGetLastError();
 }
 
@@ -563,41 +563,28 @@ hipError_t launch_rfc_state(hipStream_t s, uint32_t n, const uint32_t* stream_fi
                             wsg_stream_state* state, const RfcPlan& R, bool consumed_only)
 {
     const uint32_t grid = uint32_t((uint64_t(n_streams) + BLOCK - 1) / BLOCK);
-    if (consumed_only)
-        k_rfc_state<true><<<grid, BLOCK, 0, s>>>(n, stream_first, n_streams, state, R);
-    else
-        k_rfc_state<false><<<grid, BLOCK, 0, s>>>(n, stream_first, n_streams, state, R);
+    const auto k = consumed_only ? k_rfc_state<true> : k_rfc_state<false>;
+    k<<<grid, BLOCK, 0, s>>>(n, stream_first, n_streams, state, R);
     return hipGetLastError();
 }
 
-hipError_t launch_rfc_reply_local(hipStream_t s, bool checked, const uint8_t* wire, const wsg_recv_info* info,
-                                  uint32_t n, const MsgPlan& P, const RfcPlan& R, const ReplyRule& rule, wsg_msg* msgs,
-                                  const uint64_t* verdict)
+hipError_t launch_rfc_reply_local(hipStream_t s, bool checked, const Batch& b, const MsgOut& o, const MsgScratch& x,
+                                  const ReplyRule& rule, const uint64_t* verdict)
 {
-    const uint32_t nb = uint32_t((uint64_t(n) + BLOCK - 1) / BLOCK);
-    if (checked)
-        k_rfc_reply_local<true><<<nb, BLOCK, 0, s>>>(wire, info, n, P, R, rule, msgs, verdict);
-    else
-        k_rfc_reply_local<false><<<nb, BLOCK, 0, s>>>(wire, info, n, P, R, rule, msgs, verdict);
+    const uint32_t nb = uint32_t((uint64_t(b.n) + BLOCK - 1) / BLOCK);
+    const auto k = checked ? k_rfc_reply_local<true> : k_rfc_reply_local<false>;
+    k<<<nb, BLOCK, 0, s>>>(b.wire, o.info, b.n, x.plans.ref, x.plans.rfc, rule, o.msgs, verdict);
     return hipGetLastError();
 }
 
-hipError_t launch_rfc_reply_finalize(hipStream_t s, bool checked, const wsg_recv_info* info, uint32_t n,
-                                     const uint32_t* stream_first, uint32_t n_streams, const MsgPlan& P,
-                                     const RfcPlan& R, const ReplyRule& rule, const uint32_t* send_key,
-                                     const wsg_msg* msgs, uint8_t* reply, uint64_t reply_cap, uint64_t* reply_off,
-                                     uint64_t* stream_reply, MsgPiece* pieces, uint64_t pieces_cap,
-                                     const uint64_t* verdict, uint64_t* close_off)
+hipError_t launch_rfc_reply_finalize(hipStream_t s, bool checked, const Batch& b, const MsgOut& o, const MsgScratch& x,
+                                     const ReplyOut& r, const ReplyRule& rule, const uint64_t* verdict)
 {
-    const uint32_t nb = uint32_t((uint64_t(n) + BLOCK - 1) / BLOCK);
-    if (checked)
-        k_rfc_reply_finalize<true><<<nb, BLOCK, 0, s>>>(info, n, stream_first, n_streams, P, R, rule, send_key, msgs,
-                                                        reply, reply_cap, reply_off, stream_reply, pieces, pieces_cap,
-                                                        verdict, close_off);
-    else
-        k_rfc_reply_finalize<false><<<nb, BLOCK, 0, s>>>(info, n, stream_first, n_streams, P, R, rule, send_key, msgs,
-                                                         reply, reply_cap, reply_off, stream_reply, pieces,
-                                                         pieces_cap, verdict, close_off);
+    const uint32_t nb = uint32_t((uint64_t(b.n) + BLOCK - 1) / BLOCK);
+    const auto k = checked ? k_rfc_reply_finalize<true> : k_rfc_reply_finalize<false>;
+    k<<<nb, BLOCK, 0, s>>>(o.info, b.n, b.stream_first, b.n_streams, x.plans.ref, x.plans.rfc, rule, r.send_key, o.msgs,
+                           r.reply, r.reply_cap, r.reply_off, r.stream_reply, x.pieces, x.pieces_cap, verdict,
+                           r.close_off);
     return hipGetLastError();
 }
 

@@ -1,7 +1,9 @@
 // wsg_capi_device.cpp — the device-resident entry points of include/wsg_capi.h
-// (wsg_decode_batch through wsg_fanout_encode_many): argument checks, scratch,
-// launches.  Operands are device memory; nothing here synchronises but
-// wsg_*_streams, which read a frame count back.
+// (wsg_decode_batch through wsg_relay_validated_streams, wsg_utf8_verdicts,
+// wsg_encode_batch and the fan-outs): scratch and launches.  An entry point
+// fills the operand groups of wsg_operands.h from its parameters once; what it
+// accepts is its args_* function of wsg_args.h.  Operands are device memory;
+// nothing here synchronises but wsg_*_streams, which read a frame count back.
 #include "wsg_ctx.h"
 
 #include <vector>
@@ -29,6 +31,13 @@ namespace {
 // upper bound of the pieces: sum of ceil((size + 15) / PIECE) over frames
 inline uint64_t pieces_bound(uint32_t n, uint64_t wire_cap) { return wire_cap / wsg::PIECE + 2 * uint64_t(n) + 1; }
 
+// A wave per piece, under the caller's cap: the grid of the gathers, of
+// k_utf8_wire, of k_encode_mask and of the carry's copy.
+int piece_grid(const wsg_ctx* c, uint64_t pieces, int blocks_per_cu)
+{
+    return grid_for(c, ceil_div(pieces, wsg::BLOCK / 64), blocks_per_cu);
+}
+
 // The scratch of wsg_decode_messages / wsg_reply_messages for n frames of a
 // wire of wire_len bytes: the plan block and the piece records.  Pieces: at
 // most len / PIECE + 2 per delivered frame, and the delivered payloads of a
@@ -38,24 +47,25 @@ inline uint64_t pieces_bound(uint32_t n, uint64_t wire_cap) { return wire_cap / 
 // behind the previous call's kernels, whatever stream they ran on.
 // Under WSG_ASSEMBLY_RFC the plan block holds that rule's scans behind the
 // reference rule's (which its reply kernels and the gather share).
-int msg_scratch(wsg_ctx* c, hipStream_t s, uint32_t n, uint64_t wire_len, wsg::MsgPlans* plans, uint64_t* pieces_cap,
-                bool* ordered)
+int msg_scratch(wsg_ctx* c, hipStream_t s, uint32_t n, uint64_t wire_len, wsg::MsgScratch* x, bool* ordered)
 {
-    *pieces_cap = pieces_bound(n, wire_len);
-    if (*pieces_cap > UINT32_MAX)
+    x->pieces_cap = pieces_bound(n, wire_len);
+    if (x->pieces_cap > UINT32_MAX)
         return WSG_EINVAL;
-    plans->assembly = c->assembly;
+    x->plans.assembly = c->assembly;
     const bool rfc = c->assembly == WSG_ASSEMBLY_RFC;
     const uint64_t ref_bytes = (wsg::msg_plan_layout(nullptr, n, nullptr) + 15) & ~uint64_t(15);
     if (int rc = ensure_array(c->d_msg_plan, c->msg_plan_cap,
                               ref_bytes + (rfc ? wsg::rfc_plan_layout(nullptr, n, nullptr) : 0)))
         return rc;
-    if (int rc = ensure_array(c->d_msg_pieces, c->msg_pieces_cap, *pieces_cap))
+    if (int rc = ensure_array(c->d_msg_pieces, c->msg_pieces_cap, x->pieces_cap))
         return rc;
-    wsg::msg_plan_layout(c->d_msg_plan, n, &plans->ref);
-    plans->rfc = wsg::RfcPlan{};
+    wsg::msg_plan_layout(c->d_msg_plan, n, &x->plans.ref);
+    x->plans.rfc = wsg::RfcPlan{};
     if (rfc)
-        wsg::rfc_plan_layout(c->d_msg_plan + ref_bytes, n, &plans->rfc);
+        wsg::rfc_plan_layout(c->d_msg_plan + ref_bytes, n, &x->plans.rfc);
+    x->pieces = c->d_msg_pieces;
+    x->err = c->d_err;
     return scratch_enter(c->msg_order, s, ordered);
 }
 
@@ -75,50 +85,22 @@ int proto_scratch(wsg_ctx* c, hipStream_t s, uint32_t n, uint32_t n_streams, wsg
     return scratch_enter(c->proto_order, s, ordered);
 }
 
-// k_utf8_wire: a wave per piece record, under a cap of its own.
-int utf8_wire_grid(const wsg_ctx* c, uint64_t pieces_cap)
-{
-    return grid_for(c, ceil_div(pieces_cap, wsg::BLOCK / 64), c->utf8_wire_blocks_per_cu);
-}
-
-wsg::ReplyRule make_rule(const uint8_t reply_op[5], int mask)
-{
-    wsg::ReplyRule rule;
-    for (int k = 0; k < 5; ++k)
-        rule.op[k] = reply_op[k];
-    rule.mask = mask ? 1 : 0;
-    return rule;
-}
-
-// The gather over the plan's piece records, the timed kernel of its call:
-// `launch` is launch_msg_gather (every delivered payload byte to d_msg) or
-// launch_reply_gather (re-keyed, to the reply wire).
-int gather_launch(wsg_ctx* c, hipStream_t s, decltype(wsg::launch_msg_gather)* launch, const uint8_t* d_wire,
-                  const wsg::MsgPlan& plan, uint64_t pieces_cap, uint8_t* d_dst, uint64_t dst_cap)
+// The gather over piece records, the timed kernel of its call; tot: which
+// pieces (wsg::launch_gather).
+int gather_launch(wsg_ctx* c, hipStream_t s, const uint8_t* d_wire, const uint64_t* tot, const wsg::MsgScratch& x,
+                  uint8_t* d_dst, uint64_t dst_cap)
 {
     const int t = timing_begin(c, s);
-    WSG_HIP(launch(s, grid_for(c, ceil_div(pieces_cap, wsg::BLOCK / 64), c->enc_blocks_per_cu), d_wire, plan,
-                   c->d_msg_pieces, pieces_cap, d_dst, dst_cap));
+    WSG_HIP(wsg::launch_gather(s, piece_grid(c, x.pieces_cap, c->enc_blocks_per_cu), d_wire, tot, x.pieces,
+                               x.pieces_cap, d_dst, dst_cap));
     timing_end(c, s, t);
     return WSG_OK;
 }
 
-// What wsg_relay_validated adds to wsg_reply_validated's arguments.
-struct RelayArgs {
-    const uint8_t* relay_op;
-    const uint32_t* d_order;
-    const uint32_t* d_group_first;
-    uint32_t n_groups;
-    uint8_t* d_relay;
-    uint64_t relay_cap;
-    uint64_t* d_relay_off;
-    uint64_t* d_group_relay;
-};
-
-// Its scratch for n frames in n_streams streams: the plan block and piece
-// records of its own (the reply's gather reads the message plan's while the
-// relay's are written), the context's, under the message plan's order, which
-// the caller has entered.
+// wsg_relay_validated's scratch for n frames in n_streams streams: the plan
+// block and piece records of its own (the reply's gather reads the message
+// plan's while the relay's are written), the context's, under the message
+// plan's order, which the caller has entered.
 int relay_scratch(wsg_ctx* c, uint32_t n, uint32_t n_streams, uint64_t pieces_cap, wsg::RelayPlan* plan)
 {
     const uint64_t block = wsg::relay_plan_layout(nullptr, n, n_streams, nullptr);
@@ -135,49 +117,46 @@ int relay_scratch(wsg_ctx* c, uint32_t n, uint32_t n_streams, uint64_t pieces_ca
 int wsg_decode_batch(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const uint64_t* d_frame_start, uint32_t n,
                      uint8_t* d_out, wsg_recv_info* d_info, void* stream)
 {
-    if (!c || (wire_len && (!d_wire || !d_out)) || (n && (!d_frame_start || !d_info)))
-        return WSG_EINVAL;
-    if (!aligned16(d_wire) || !aligned16(d_out))
-        return WSG_EINVAL;
-    if (c->check && (!in_alloc(d_wire, (wire_len + 15) & ~uint64_t(15)) || !in_alloc(d_out, wire_len) ||
-                     !in_alloc(d_frame_start, uint64_t(n) * 8) || !in_alloc(d_info, uint64_t(n) * sizeof(wsg_recv_info))))
+    if (!c || wsg::args_decode_batch(d_wire, wire_len, d_frame_start, n, d_out, d_info, c->check))
         return WSG_EINVAL;
     return decode_launch(c, d_wire, wire_len, d_frame_start, n, d_out, d_info, as_stream(stream), c->d_err);
 }
 
+namespace {
+
 // Messages out of a batch of frames: the plan pass (a few small kernels, one
 // lane per frame or per stream), then the gather, which moves every
-// delivered payload byte once.
+// delivered payload byte once, to d_msg.  r (wsg_reply_messages): the plan
+// with the reply frames' geometry scanned behind it, then the same gather, its
+// destination the reply wire.
+int messages(wsg_ctx* c, const wsg::Batch& b, wsg_stream_state* d_state, uint8_t* d_msg, uint64_t msg_cap,
+             const wsg::ReplyOut* r, const wsg::MsgOut& o, void* stream)
+{
+    if (!c || wsg::args_messages(b, d_state, d_msg, msg_cap, r, o, nullptr, nullptr, nullptr, nullptr, c->check))
+        return WSG_EINVAL;
+    hipStream_t s = as_stream(stream);
+    wsg::MsgScratch x;
+    bool ordered = false;
+    if (int rc = msg_scratch(c, s, b.n, b.wire_len, &x, &ordered))
+        return rc;
+    WSG_HIP(r ? wsg::launch_reply_plan(s, b, d_state, *r, o, x)
+              : wsg::launch_msg_plan(s, b, d_state, d_state, msg_cap, o, x));
+    if (b.n)
+        if (int rc = r ? gather_launch(c, s, b.wire, x.plans.ref.rtot, x, r->reply, r->reply_cap)
+                       : gather_launch(c, s, b.wire, x.plans.ref.tot, x, d_msg, msg_cap))
+            return rc;
+    return scratch_leave(c->msg_order, s, ordered);
+}
+
+} // namespace
+
 int wsg_decode_messages(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const uint64_t* d_frame_start,
                         uint32_t n, const uint32_t* d_stream_first, uint32_t n_streams, wsg_stream_state* d_state,
                         uint8_t* d_msg, uint64_t msg_cap, wsg_msg* d_msgs, uint64_t* d_count, wsg_recv_info* d_info,
                         void* stream)
 {
-    if (!c || !d_count || !d_stream_first || (wire_len && !d_wire) || (msg_cap && !d_msg) ||
-        (n && (!d_frame_start || !d_info || !d_msgs || n_streams == 0)) || (n_streams && !d_state) ||
-        n == UINT32_MAX || n_streams == UINT32_MAX)
-        return WSG_EINVAL;
-    if (!aligned16(d_wire) || !aligned16(d_msg))
-        return WSG_EINVAL;
-    if (c->check &&
-        (!in_alloc(d_wire, (wire_len + 15) & ~uint64_t(15)) || !in_alloc(d_frame_start, uint64_t(n) * 8) ||
-         !in_alloc(d_stream_first, (uint64_t(n_streams) + 1) * 4) ||
-         !in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) || !in_alloc(d_msg, msg_cap) ||
-         !in_alloc(d_msgs, uint64_t(n) * sizeof(wsg_msg)) || !in_alloc(d_count, 2 * 8) ||
-         !in_alloc(d_info, uint64_t(n) * sizeof(wsg_recv_info))))
-        return WSG_EINVAL;
-    hipStream_t s = as_stream(stream);
-    wsg::MsgPlans plan;
-    uint64_t pieces_cap;
-    bool ordered = false;
-    if (int rc = msg_scratch(c, s, n, wire_len, &plan, &pieces_cap, &ordered))
-        return rc;
-    WSG_HIP(wsg::launch_msg_plan(s, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams, d_state, msg_cap,
-                                 d_msgs, d_count, d_info, plan, c->d_msg_pieces, pieces_cap, c->d_err));
-    if (n)
-        if (int rc = gather_launch(c, s, wsg::launch_msg_gather, d_wire, plan.ref, pieces_cap, d_msg, msg_cap))
-            return rc;
-    return scratch_leave(c->msg_order, s, ordered);
+    const wsg::Batch b{d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams};
+    return messages(c, b, d_state, d_msg, msg_cap, nullptr, wsg::MsgOut{d_msgs, d_count, d_info}, stream);
 }
 
 // UTF-8 over the messages of a decode: one lane per record before and behind
@@ -185,13 +164,7 @@ int wsg_decode_messages(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, co
 int wsg_check_utf8(wsg_ctx* c, const uint8_t* d_msg, uint64_t msg_cap, const wsg_msg* d_msgs, const uint64_t* d_count,
                    uint32_t msg_room, uint32_t which, uint64_t* d_valid, uint64_t* d_result, void* stream)
 {
-    if (!c || !d_count || !d_result || (msg_cap && !d_msg) || (msg_room && (!d_msgs || !d_valid)))
-        return WSG_EINVAL;
-    if (!aligned16(d_msg) || !aligned8(d_msgs) || !aligned8(d_count) || !aligned8(d_valid) || !aligned8(d_result))
-        return WSG_EINVAL;
-    if (c->check && (!in_alloc(d_msg, msg_cap) || !in_alloc(d_msgs, uint64_t(msg_room) * sizeof(wsg_msg)) ||
-                     !in_alloc(d_valid, uint64_t(msg_room) * 8) || !in_alloc(d_count, 2 * 8) ||
-                     !in_alloc(d_result, 4 * 8)))
+    if (!c || wsg::args_check_utf8(d_msg, msg_cap, d_msgs, d_count, msg_room, d_valid, d_result, c->check))
         return WSG_EINVAL;
     hipStream_t s = as_stream(stream);
     const int rec_grid = grid_for(c, ceil_div(msg_room, wsg::BLOCK));   // (at least one block: it seeds d_result)
@@ -217,36 +190,23 @@ int wsg_check_utf8_wire(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, co
                         const wsg_stream_state* d_state, uint32_t which, wsg_msg* d_msgs, uint64_t* d_count,
                         wsg_recv_info* d_info, uint64_t* d_valid, uint64_t* d_result, void* stream)
 {
-    if (!c || !d_count || !d_result || !d_stream_first || (wire_len && !d_wire) ||
-        (n && (!d_frame_start || !d_info || !d_msgs || !d_valid || n_streams == 0)) || (n_streams && !d_state) ||
-        n == UINT32_MAX || n_streams == UINT32_MAX)
-        return WSG_EINVAL;
-    if (!aligned16(d_wire) || !aligned8(d_frame_start) || (reinterpret_cast<uintptr_t>(d_stream_first) & 3u) ||
-        !aligned8(d_state) || !aligned8(d_msgs) || !aligned8(d_count) || !aligned8(d_info) || !aligned8(d_valid) ||
-        !aligned8(d_result))
-        return WSG_EINVAL;
-    if (c->check &&
-        (!in_alloc(d_wire, (wire_len + 15) & ~uint64_t(15)) || !in_alloc(d_frame_start, uint64_t(n) * 8) ||
-         !in_alloc(d_stream_first, (uint64_t(n_streams) + 1) * 4) ||
-         !in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) ||
-         !in_alloc(d_msgs, uint64_t(n) * sizeof(wsg_msg)) || !in_alloc(d_count, 2 * 8) ||
-         !in_alloc(d_info, uint64_t(n) * sizeof(wsg_recv_info)) || !in_alloc(d_valid, uint64_t(n) * 8) ||
-         !in_alloc(d_result, 4 * 8)))
+    const wsg::Batch b{d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams};
+    const wsg::MsgOut o{d_msgs, d_count, d_info};
+    const wsg::Utf8Inside u{which, d_valid, d_result, /*also*/ nullptr, /*grids*/ 1, 1};
+    if (!c || wsg::args_messages(b, d_state, nullptr, 0, nullptr, o, nullptr, &u, nullptr, nullptr, c->check))
         return WSG_EINVAL;
     hipStream_t s = as_stream(stream);
-    wsg::MsgPlans plan;
-    uint64_t pieces_cap;
+    wsg::MsgScratch x;
     bool ordered = false;
-    if (int rc = msg_scratch(c, s, n, wire_len, &plan, &pieces_cap, &ordered))
+    if (int rc = msg_scratch(c, s, n, wire_len, &x, &ordered))
         return rc;
-    WSG_HIP(wsg::launch_msg_plan_only(s, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams, d_state,
-                                      d_msgs, d_count, d_info, plan, c->d_msg_pieces, pieces_cap, c->d_err));
+    WSG_HIP(wsg::launch_msg_plan(s, b, nullptr, d_state, UINT64_MAX, o, x));
     const int rec_grid = grid_for(c, ceil_div(n, wsg::BLOCK));   // (at least one block: it seeds d_result)
     WSG_HIP(wsg::launch_utf8_init(s, rec_grid, d_msgs, d_count, n, d_valid, d_result));
     if (n && which) {
         const int t = timing_begin(c, s);
-        WSG_HIP(wsg::launch_utf8_wire(s, utf8_wire_grid(c, pieces_cap), d_wire, wire_len, plan.ref, c->d_msg_pieces,
-                                      pieces_cap, d_msgs, d_count, n, which, d_valid));
+        WSG_HIP(wsg::launch_utf8_wire(s, piece_grid(c, x.pieces_cap, c->utf8_wire_blocks_per_cu), b, o, x, which,
+                                      d_valid));
         timing_end(c, s, t);
     }
     WSG_HIP(wsg::launch_utf8_count(s, rec_grid, d_msgs, d_count, n, UINT64_MAX, which, d_valid, d_result));
@@ -261,32 +221,22 @@ int wsg_check_protocol(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, con
                        wsg_proto_state* d_proto, uint32_t role, uint64_t max_message, wsg_proto_verdict* d_verdict,
                        uint64_t* d_result, void* stream)
 {
-    if (!c || !d_info || !d_stream_first || !d_proto || !d_verdict || !d_result || (wire_len && !d_wire) ||
-        role > WSG_PROTO_CLIENT || n == UINT32_MAX || n_streams == UINT32_MAX)
-        return WSG_EINVAL;
-    if (!aligned8(d_info) || (reinterpret_cast<uintptr_t>(d_stream_first) & 3u) || !aligned8(d_state) ||
-        !aligned8(d_proto) || !aligned8(d_verdict) || !aligned8(d_result))
-        return WSG_EINVAL;
-    if (c->check && (!in_alloc(d_wire, wire_len) || !in_alloc(d_info, uint64_t(n) * sizeof(wsg_recv_info)) ||
-                     !in_alloc(d_stream_first, (uint64_t(n_streams) + 1) * 4) ||
-                     (d_state && !in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state))) ||
-                     !in_alloc(d_proto, uint64_t(n_streams) * sizeof(wsg_proto_state)) ||
-                     !in_alloc(d_verdict, uint64_t(n_streams) * sizeof(wsg_proto_verdict)) || !in_alloc(d_result, 3 * 8)))
+    const wsg::Batch b{d_wire, wire_len, /*fs*/ nullptr, n, d_stream_first, n_streams};
+    const wsg::ProtoOps p{d_proto, role, max_message, /*also*/ nullptr, d_verdict, d_result};
+    if (!c || wsg::args_check_protocol(b, d_info, d_state, p, c->check))
         return WSG_EINVAL;
     hipStream_t s = as_stream(stream);
     wsg::ProtoPlan plan;
     bool ordered = false;
     if (int rc = proto_scratch(c, s, n, n_streams, &plan, &ordered))
         return rc;
-    WSG_HIP(wsg::launch_proto_scan(s, d_info, n, d_stream_first, n_streams, d_proto, plan, d_verdict, d_result));
+    WSG_HIP(wsg::launch_proto_scan(s, b, d_info, p, plan));
     if (n && n_streams) {
         const int t = timing_begin(c, s);
-        WSG_HIP(wsg::launch_proto_judge(s, d_wire, wire_len, d_info, n, d_stream_first, d_state, d_proto, role,
-                                        max_message, plan, d_verdict));
+        WSG_HIP(wsg::launch_proto_judge(s, b, d_info, d_state, p, plan));
         timing_end(c, s, t);
     }
-    WSG_HIP(wsg::launch_proto_finish(s, grid_for(c, ceil_div(n_streams, wsg::BLOCK)), n, d_stream_first, n_streams,
-                                     d_state, d_proto, plan, d_verdict, d_result));
+    WSG_HIP(wsg::launch_proto_finish(s, grid_for(c, ceil_div(n_streams, wsg::BLOCK)), b, d_state, p, plan));
     return scratch_leave(c->proto_order, s, ordered);
 }
 
@@ -296,16 +246,8 @@ int wsg_frame_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_
                       uint32_t n_streams, uint64_t* d_frame_start, uint32_t frame_cap, uint32_t* d_stream_first,
                       uint64_t* d_count, void* stream)
 {
-    if (!c || !d_count || !d_stream_first || (wire_len && !d_wire) || (n_streams && !d_span) ||
-        (frame_cap && !d_frame_start) || n_streams == UINT32_MAX)
-        return WSG_EINVAL;
-    if (!aligned16(d_wire))
-        return WSG_EINVAL;
-    if (c->check &&
-        (!in_alloc(d_wire, (wire_len + 15) & ~uint64_t(15)) ||
-         !in_alloc(d_span, uint64_t(n_streams) * sizeof(wsg_stream_span)) ||
-         !in_alloc(d_frame_start, uint64_t(frame_cap) * 8) ||
-         !in_alloc(d_stream_first, (uint64_t(n_streams) + 1) * 4) || !in_alloc(d_count, 2 * 8)))
+    if (!c || wsg::args_frame_streams(d_wire, wire_len, d_span, n_streams, d_frame_start, frame_cap, d_stream_first,
+                                      d_count, c->check))
         return WSG_EINVAL;
     hipStream_t s = as_stream(stream);
     if (int rc = ensure_array(c->d_frame_plan, c->frame_plan_cap, wsg::frame_plan_layout(nullptr, n_streams, nullptr)))
@@ -332,16 +274,8 @@ int wsg_upgrade_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, ws
                         uint32_t n_streams, uint64_t max_request, wsg_upgrade* d_up, uint8_t* d_resp,
                         uint64_t resp_cap, uint64_t* d_resp_off, uint64_t* d_count, void* stream)
 {
-    if (!c || !d_count || !d_resp_off || (wire_len && !d_wire) || (n_streams && (!d_span || !d_up)) ||
-        (resp_cap && !d_resp) || n_streams == UINT32_MAX)
-        return WSG_EINVAL;
-    if (!aligned16(d_wire) || !aligned16(d_resp) || !aligned8(d_span) || !aligned8(d_up) || !aligned8(d_resp_off) ||
-        !aligned8(d_count))
-        return WSG_EINVAL;
-    if (c->check && (!in_alloc(d_wire, (wire_len + 15) & ~uint64_t(15)) ||
-                     !in_alloc(d_span, uint64_t(n_streams) * sizeof(wsg_stream_span)) ||
-                     !in_alloc(d_up, uint64_t(n_streams) * sizeof(wsg_upgrade)) || !in_alloc(d_resp, resp_cap) ||
-                     !in_alloc(d_resp_off, (uint64_t(n_streams) + 1) * 8) || !in_alloc(d_count, 4 * 8)))
+    if (!c || wsg::args_upgrade_streams(d_wire, wire_len, d_span, n_streams, d_up, d_resp, resp_cap, d_resp_off,
+                                        d_count, c->check))
         return WSG_EINVAL;
     hipStream_t s = as_stream(stream);
     if (int rc = ensure_array(c->d_frame_plan, c->frame_plan_cap, wsg::upgrade_plan_layout(nullptr, n_streams, nullptr)))
@@ -367,24 +301,8 @@ int wsg_carry_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, cons
                       const wsg_stream_read* d_read, uint8_t* d_next, uint64_t next_cap, wsg_stream_span* d_next_span,
                       uint64_t* d_count, void* stream)
 {
-    if (!c || !d_count || (wire_len && !d_wire) || (new_len && !d_new) || (next_cap && !d_next) ||
-        (n_streams && (!d_span || !d_next_span)) || n_streams == UINT32_MAX)
-        return WSG_EINVAL;
-    if (!aligned16(d_wire) || !aligned16(d_new) || !aligned16(d_next) || !aligned8(d_span) || !aligned8(d_close_off) ||
-        !aligned8(d_read) || !aligned8(d_next_span) || !aligned8(d_count))
-        return WSG_EINVAL;
-    const auto overlap = [](const uint8_t* a, uint64_t an, const uint8_t* b, uint64_t bn) {
-        return an && bn && a < b + bn && b < a + an;
-    };
-    if ((n_streams && d_next_span == d_span) || overlap(d_next, next_cap, d_wire, wire_len) ||
-        overlap(d_next, next_cap, d_new, new_len))
-        return WSG_EINVAL;
-    if (c->check &&
-        (!in_alloc(d_wire, (wire_len + 15) & ~uint64_t(15)) || !in_alloc(d_new, (new_len + 15) & ~uint64_t(15)) ||
-         !in_alloc(d_next, next_cap) || !in_alloc(d_span, uint64_t(n_streams) * sizeof(wsg_stream_span)) ||
-         (d_close_off && !in_alloc(d_close_off, uint64_t(n_streams) * 8)) ||
-         (d_read && !in_alloc(d_read, uint64_t(n_streams) * sizeof(wsg_stream_read))) ||
-         !in_alloc(d_next_span, uint64_t(n_streams) * sizeof(wsg_stream_span)) || !in_alloc(d_count, 4 * 8)))
+    if (!c || wsg::args_carry_streams(d_wire, wire_len, d_span, n_streams, d_close_off, d_new, new_len, d_read, d_next,
+                                      next_cap, d_next_span, d_count, c->check))
         return WSG_EINVAL;
     hipStream_t s = as_stream(stream);
     if (int rc = ensure_array(c->d_frame_plan, c->frame_plan_cap, wsg::carry_plan_layout(nullptr, n_streams, nullptr)))
@@ -401,8 +319,8 @@ int wsg_carry_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, cons
     const uint64_t most = std::min(next_cap, wire_len + new_len + uint64_t(n_streams) * wsg::CHUNK);
     if (n_streams && most) {
         const int t = timing_begin(c, s);
-        WSG_HIP(wsg::launch_carry_copy(s, grid_for(c, ceil_div(ceil_div(most, wsg::PIECE), wsg::BLOCK / 64), c->dec_blocks_per_cu),
-                                       d_wire, d_new, n_streams, plan, d_next, next_cap));
+        WSG_HIP(wsg::launch_carry_copy(s, piece_grid(c, ceil_div(most, wsg::PIECE), c->dec_blocks_per_cu), d_wire,
+                                       d_new, n_streams, plan, d_next, next_cap));
         timing_end(c, s, t);
     }
     return scratch_leave(c->frame_order, s, ordered);
@@ -410,35 +328,36 @@ int wsg_carry_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, cons
 
 namespace {
 
-// wsg_decode_streams and wsg_reply_streams: the framer, one synchronisation
-// to read the frame count, `messages(n)` over the frames it found, the spans'
-// consumed lowered to the first tail frame.
+// The _streams forms: the framer, one synchronisation to read the frame
+// count, `messages(the batch of the frames it found)`, the spans' consumed
+// lowered to the first tail frame.  b: the batch at n = f.frame_cap, which the
+// caller has checked.
 template <class Messages>
-int streams_then(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_stream_span* d_span, uint32_t n_streams,
-                 wsg_stream_state* d_state, uint64_t* d_frame_start, uint32_t frame_cap, uint32_t* d_stream_first,
-                 uint64_t* d_count, uint32_t* n_frames_out, void* stream, Messages messages)
+int streams_then(wsg_ctx* c, const wsg::Batch& b, const wsg::Framed& f, wsg_stream_state* d_state, uint64_t* d_count,
+                 void* stream, Messages messages)
 {
     hipStream_t s = as_stream(stream);
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     WSG_HIP(hipStreamIsCapturing(s, &cap));
     if (cap != hipStreamCaptureStatusNone)
         return WSG_EINVAL;   // the frame count is read on the host in the middle
-    *n_frames_out = 0;
-    if (int rc = wsg_frame_streams(c, d_wire, wire_len, d_span, n_streams, d_frame_start, frame_cap, d_stream_first,
-                                   d_count, stream))
+    *f.n_frames_out = 0;
+    if (int rc = wsg_frame_streams(c, b.wire, b.wire_len, f.span, b.n_streams, f.frame_start, f.frame_cap,
+                                   f.stream_first, d_count, stream))
         return rc;
     uint64_t found = 0;
     WSG_HIP(hipMemcpyAsync(&found, d_count, sizeof(found), hipMemcpyDeviceToHost, s));
     WSG_HIP(hipStreamSynchronize(s));
     if (found > uint64_t(UINT32_MAX) - 1)
         return WSG_EINVAL;
-    if (found > frame_cap)
+    if (found > f.frame_cap)
         return WSG_ENOMEM;
-    const uint32_t n = uint32_t(found);
-    *n_frames_out = n;
-    if (int rc = messages(n))
+    wsg::Batch frames = b;
+    frames.n = uint32_t(found);
+    *f.n_frames_out = frames.n;
+    if (int rc = messages(frames))
         return rc;
-    WSG_HIP(wsg::launch_frame_tail(s, d_span, n_streams, d_frame_start, d_stream_first, d_state, n));
+    WSG_HIP(wsg::launch_frame_tail(s, f.span, b.n_streams, f.frame_start, f.stream_first, d_state, frames.n));
     return WSG_OK;
 }
 
@@ -449,59 +368,97 @@ int wsg_decode_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg
                        uint32_t* d_stream_first, uint8_t* d_msg, uint64_t msg_cap, wsg_msg* d_msgs, uint64_t* d_count,
                        wsg_recv_info* d_info, uint32_t* n_frames_out, void* stream)
 {
-    if (!c || !n_frames_out || !d_count || (n_streams && !d_state) || (msg_cap && !d_msg) ||
-        (frame_cap && (!d_msgs || !d_info)) || !aligned16(d_msg))
+    const wsg::Framed f{d_span, d_frame_start, frame_cap, d_stream_first, n_frames_out};
+    // (every frame the framer has room for)
+    const wsg::Batch b{d_wire, wire_len, f.frame_start, f.frame_cap, f.stream_first, n_streams};
+    const wsg::MsgOut o{d_msgs, d_count, d_info};
+    if (!c || wsg::args_messages(b, d_state, d_msg, msg_cap, nullptr, o, nullptr, nullptr, nullptr, &f, c->check))
         return WSG_EINVAL;
-    if (c->check && (!in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) || !in_alloc(d_msg, msg_cap) ||
-                     !in_alloc(d_msgs, uint64_t(frame_cap) * sizeof(wsg_msg)) ||
-                     !in_alloc(d_info, uint64_t(frame_cap) * sizeof(wsg_recv_info))))
-        return WSG_EINVAL;
-    return streams_then(c, d_wire, wire_len, d_span, n_streams, d_state, d_frame_start, frame_cap, d_stream_first,
-                        d_count, n_frames_out, stream, [&](uint32_t n) {
-                            return wsg_decode_messages(c, d_wire, wire_len, d_frame_start, n, d_stream_first,
-                                                       n_streams, d_state, d_msg, msg_cap, d_msgs, d_count, d_info,
-                                                       stream);
-                        });
+    return streams_then(c, b, f, d_state, d_count, stream, [&](const wsg::Batch& frames) {
+        return messages(c, frames, d_state, d_msg, msg_cap, nullptr, o, stream);
+    });
 }
 
-// Replies out of a batch of frames: wsg_decode_messages' plan with the reply
-// frames' geometry scanned behind it, then the same gather, its destination
-// the reply wire.
+namespace {
+
+// wsg_reply_messages with wsg_check_protocol inside it: the protocol kernels
+// run on the d_info the plan's header pass has just written, and the reply
+// kernels stop every stream at its terminal frame and close it there.
+// utf8 (wsg_reply_validated): the UTF-8 check from the wire inside the plan,
+// d_valid and d_utf8_result written, its verdicts merged with p.also.
+// relay (wsg_relay_validated): the relay's plan and gather behind the reply side.
+int reply_checked(wsg_ctx* c, const wsg::Batch& b, wsg_stream_state* d_state, const wsg::ProtoOps& p,
+                  const wsg::ReplyOut& r, const wsg::MsgOut& o, const wsg::Utf8Inside* utf8,
+                  const wsg::RelayArgs* relay, void* stream)
+{
+    if (!c || wsg::args_messages(b, d_state, nullptr, 0, &r, o, &p, utf8, relay, nullptr, c->check))
+        return WSG_EINVAL;
+    bool relays = false;   // a kind is relayed: the relay's gather has something to move
+    for (int k = 1; relay && k < 5; ++k)
+        relays = relays || relay->relay_op[k];
+    hipStream_t s = as_stream(stream);
+    // both scratches are the context's: behind the last user of either,
+    // whatever stream it ran on
+    wsg::ProtoPlan pplan;
+    wsg::MsgScratch x;
+    bool ordered = false, pordered = false;
+    wsg::Utf8Inside u = utf8 ? *utf8 : wsg::Utf8Inside{};
+    if (int rc = proto_scratch(c, s, b.n, b.n_streams, &pplan, &pordered, utf8 ? &u.also : nullptr))
+        return rc;
+    if (int rc = msg_scratch(c, s, b.n, b.wire_len, &x, &ordered))
+        return rc;
+    wsg::RelayPlan rplan;
+    if (relay)
+        if (int rc = relay_scratch(c, b.n, b.n_streams, x.pieces_cap, &rplan))
+            return rc;
+    u.rec_grid = grid_for(c, ceil_div(b.n, wsg::BLOCK));
+    u.wire_grid = piece_grid(c, x.pieces_cap, c->utf8_wire_blocks_per_cu);
+    WSG_HIP(wsg::launch_reply_checked_plan(s, grid_for(c, ceil_div(b.n_streams, wsg::BLOCK)), b, d_state, p, pplan, r,
+                                           o, x, utf8 ? &u : nullptr));
+    if (b.n)
+        if (int rc = gather_launch(c, s, b.wire, x.plans.ref.rtot, x, r.reply, r.reply_cap))
+            return rc;
+    if (relay) {
+        // behind the whole reply side, which it reads (d_info, d_msgs, d_verdict) and leaves as it is
+        wsg::MsgScratch rx = x;
+        rx.pieces = c->d_relay_pieces;
+        WSG_HIP(wsg::launch_relay_plan(s, b, o, p.verdict, *relay, rplan, rx));
+        if (b.n && relays)
+            if (int rc = gather_launch(c, s, b.wire, rplan.gtot, rx, relay->relay, relay->relay_cap))
+                return rc;
+    }
+    if (int rc = scratch_leave(c->proto_order, s, pordered))
+        return rc;
+    return scratch_leave(c->msg_order, s, ordered);
+}
+
+// The _streams form of the replies: of messages() (p null) and of reply_checked.
+int reply_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, uint32_t n_streams, const wsg::Framed& f,
+                  wsg_stream_state* d_state, const wsg::ProtoOps* p, const wsg::ReplyOut& r, const wsg::MsgOut& o,
+                  const wsg::Utf8Inside* utf8, const wsg::RelayArgs* relay, void* stream)
+{
+    // (every frame the framer has room for)
+    const wsg::Batch b{d_wire, wire_len, f.frame_start, f.frame_cap, f.stream_first, n_streams};
+    if (!c || wsg::args_messages(b, d_state, nullptr, 0, &r, o, p, utf8, relay, &f, c->check))
+        return WSG_EINVAL;
+    return streams_then(c, b, f, d_state, o.count, stream, [&](const wsg::Batch& frames) {
+        return p ? reply_checked(c, frames, d_state, *p, r, o, utf8, relay, stream)
+                 : messages(c, frames, d_state, nullptr, 0, &r, o, stream);
+    });
+}
+
+} // namespace
+
 int wsg_reply_messages(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const uint64_t* d_frame_start, uint32_t n,
                        const uint32_t* d_stream_first, uint32_t n_streams, wsg_stream_state* d_state,
                        const uint8_t reply_op[5], int mask, const uint32_t* d_send_key, uint8_t* d_reply,
                        uint64_t reply_cap, uint64_t* d_reply_off, uint64_t* d_stream_reply, wsg_msg* d_msgs,
                        uint64_t* d_count, wsg_recv_info* d_info, void* stream)
 {
-    if (!c || !d_count || !d_stream_first || !reply_op || !d_reply_off || !d_stream_reply || (wire_len && !d_wire) ||
-        (reply_cap && !d_reply) || (n && (!d_frame_start || !d_info || !d_msgs || n_streams == 0)) ||
-        (n_streams && !d_state) || n == UINT32_MAX || n_streams == UINT32_MAX)
-        return WSG_EINVAL;
-    if (!aligned16(d_wire) || !aligned16(d_reply))
-        return WSG_EINVAL;
-    if (c->check &&
-        (!in_alloc(d_wire, (wire_len + 15) & ~uint64_t(15)) || !in_alloc(d_frame_start, uint64_t(n) * 8) ||
-         !in_alloc(d_stream_first, (uint64_t(n_streams) + 1) * 4) ||
-         !in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) ||
-         (d_send_key && !in_alloc(d_send_key, uint64_t(n_streams) * 4)) || !in_alloc(d_reply, reply_cap) ||
-         !in_alloc(d_reply_off, (uint64_t(n) + 1) * 8) || !in_alloc(d_stream_reply, (uint64_t(n_streams) + 1) * 8) ||
-         !in_alloc(d_msgs, uint64_t(n) * sizeof(wsg_msg)) || !in_alloc(d_count, 4 * 8) ||
-         !in_alloc(d_info, uint64_t(n) * sizeof(wsg_recv_info))))
-        return WSG_EINVAL;
-    hipStream_t s = as_stream(stream);
-    wsg::MsgPlans plan;
-    uint64_t pieces_cap;
-    bool ordered = false;
-    if (int rc = msg_scratch(c, s, n, wire_len, &plan, &pieces_cap, &ordered))
-        return rc;
-    WSG_HIP(wsg::launch_reply_plan(s, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams, d_state,
-                                   make_rule(reply_op, mask), d_send_key, d_reply, reply_cap, d_reply_off,
-                                   d_stream_reply, d_msgs, d_count, d_info, plan, c->d_msg_pieces, pieces_cap,
-                                   c->d_err));
-    if (n)
-        if (int rc = gather_launch(c, s, wsg::launch_reply_gather, d_wire, plan.ref, pieces_cap, d_reply, reply_cap))
-            return rc;
-    return scratch_leave(c->msg_order, s, ordered);
+    const wsg::Batch b{d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams};
+    const wsg::ReplyOut r{reply_op, mask, d_send_key, d_reply, reply_cap, d_reply_off, d_stream_reply,
+                          /*close_off*/ nullptr};
+    return messages(c, b, d_state, nullptr, 0, &r, wsg::MsgOut{d_msgs, d_count, d_info}, stream);
 }
 
 int wsg_reply_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_stream_span* d_span,
@@ -510,139 +467,12 @@ int wsg_reply_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_
                       uint8_t* d_reply, uint64_t reply_cap, uint64_t* d_reply_off, uint64_t* d_stream_reply,
                       wsg_msg* d_msgs, uint64_t* d_count, wsg_recv_info* d_info, uint32_t* n_frames_out, void* stream)
 {
-    if (!c || !n_frames_out || !d_count || !reply_op || !d_reply_off || !d_stream_reply || (n_streams && !d_state) ||
-        (reply_cap && !d_reply) || (frame_cap && (!d_msgs || !d_info)) || !aligned16(d_reply))
-        return WSG_EINVAL;
-    if (c->check &&
-        (!in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) || !in_alloc(d_reply, reply_cap) ||
-         !in_alloc(d_reply_off, (uint64_t(frame_cap) + 1) * 8) ||
-         !in_alloc(d_msgs, uint64_t(frame_cap) * sizeof(wsg_msg)) ||
-         !in_alloc(d_info, uint64_t(frame_cap) * sizeof(wsg_recv_info))))
-        return WSG_EINVAL;
-    return streams_then(c, d_wire, wire_len, d_span, n_streams, d_state, d_frame_start, frame_cap, d_stream_first,
-                        d_count, n_frames_out, stream, [&](uint32_t n) {
-                            return wsg_reply_messages(c, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams,
-                                                      d_state, reply_op, mask, d_send_key, d_reply, reply_cap,
-                                                      d_reply_off, d_stream_reply, d_msgs, d_count, d_info, stream);
-                        });
+    const wsg::Framed f{d_span, d_frame_start, frame_cap, d_stream_first, n_frames_out};
+    const wsg::ReplyOut r{reply_op, mask, d_send_key, d_reply, reply_cap, d_reply_off, d_stream_reply,
+                          /*close_off*/ nullptr};
+    return reply_streams(c, d_wire, wire_len, n_streams, f, d_state, nullptr, r, wsg::MsgOut{d_msgs, d_count, d_info},
+                         nullptr, nullptr, stream);
 }
-
-// wsg_reply_messages with wsg_check_protocol inside it: the protocol kernels
-// run on the d_info the plan's header pass has just written, and the reply
-// kernels stop every stream at its terminal frame and close it there.
-// `validated` (wsg_reply_validated): the UTF-8 check from the wire inside the
-// plan, d_valid and d_utf8_result written, its verdicts merged with d_also.
-namespace {
-
-int reply_checked(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const uint64_t* d_frame_start, uint32_t n,
-                  const uint32_t* d_stream_first, uint32_t n_streams, wsg_stream_state* d_state,
-                  wsg_proto_state* d_proto, uint32_t role, uint64_t max_message, const wsg_proto_verdict* d_also,
-                  const uint8_t reply_op[5], int mask, const uint32_t* d_send_key, uint8_t* d_reply,
-                  uint64_t reply_cap, uint64_t* d_reply_off, uint64_t* d_stream_reply, uint64_t* d_close_off,
-                  wsg_proto_verdict* d_verdict, uint64_t* d_result, wsg_msg* d_msgs, uint64_t* d_count,
-                  wsg_recv_info* d_info, void* stream, bool validated, uint32_t which, uint64_t* d_valid,
-                  uint64_t* d_utf8_result, const RelayArgs* relay = nullptr)
-{
-    bool relays = false;   // a kind is relayed: the relay's gather has something to move
-    if (relay) {
-        const RelayArgs& r = *relay;
-        if (!r.relay_op || !reply_op || !r.d_group_relay || (r.relay_cap && !r.d_relay) || (n && !r.d_relay_off) ||
-            (!r.d_group_first && r.n_groups != 1) || (r.n_groups == 0 && n_streams != 0) || r.n_groups == UINT32_MAX)
-            return WSG_EINVAL;
-        for (int k = 0; k < 5; ++k) {
-            if (r.relay_op[k] && reply_op[k])
-                return WSG_EINVAL;   // a kind is replied to or relayed, not both
-            relays = relays || (k >= 1 && r.relay_op[k]);
-        }
-        if (!aligned16(r.d_relay) || !aligned8(r.d_relay_off) || !aligned8(r.d_group_relay) ||
-            (reinterpret_cast<uintptr_t>(r.d_order) & 3u) || (reinterpret_cast<uintptr_t>(r.d_group_first) & 3u))
-            return WSG_EINVAL;
-        if (c && c->check &&
-            (!in_alloc(r.d_relay, r.relay_cap) || !in_alloc(r.d_relay_off, uint64_t(n) * 8) ||
-             !in_alloc(r.d_group_relay, (uint64_t(r.n_groups) + 1) * 8) || !in_alloc(d_count, 8 * 8) ||
-             (r.d_order && !in_alloc(r.d_order, uint64_t(n_streams) * 4)) ||
-             (r.d_group_first && !in_alloc(r.d_group_first, (uint64_t(r.n_groups) + 1) * 4))))
-            return WSG_EINVAL;
-    }
-    if (validated) {
-        if (!d_utf8_result || (n && !d_valid) || !aligned8(d_valid) || !aligned8(d_utf8_result))
-            return WSG_EINVAL;
-        if (c && c->check && (!in_alloc(d_valid, uint64_t(n) * 8) || !in_alloc(d_utf8_result, 4 * 8)))
-            return WSG_EINVAL;
-    }
-    if (!c || !d_count || !d_stream_first || !reply_op || !d_reply_off || !d_stream_reply || !d_close_off ||
-        !d_proto || !d_verdict || !d_result || (wire_len && !d_wire) || (reply_cap && !d_reply) ||
-        (n && (!d_frame_start || !d_info || !d_msgs || n_streams == 0)) || (n_streams && !d_state) ||
-        role > WSG_PROTO_CLIENT || n == UINT32_MAX || n_streams == UINT32_MAX)
-        return WSG_EINVAL;
-    if (!aligned16(d_wire) || !aligned16(d_reply))
-        return WSG_EINVAL;
-    if (!aligned8(d_frame_start) || (reinterpret_cast<uintptr_t>(d_stream_first) & 3u) || !aligned8(d_state) ||
-        !aligned8(d_proto) || !aligned8(d_also) || (reinterpret_cast<uintptr_t>(d_send_key) & 3u) ||
-        !aligned8(d_reply_off) || !aligned8(d_stream_reply) || !aligned8(d_close_off) || !aligned8(d_verdict) ||
-        !aligned8(d_result) || !aligned8(d_msgs) || !aligned8(d_count) || !aligned8(d_info))
-        return WSG_EINVAL;
-    if (c->check &&
-        (!in_alloc(d_wire, (wire_len + 15) & ~uint64_t(15)) || !in_alloc(d_frame_start, uint64_t(n) * 8) ||
-         !in_alloc(d_stream_first, (uint64_t(n_streams) + 1) * 4) ||
-         !in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) ||
-         !in_alloc(d_proto, uint64_t(n_streams) * sizeof(wsg_proto_state)) ||
-         (d_also && !in_alloc(d_also, uint64_t(n_streams) * sizeof(wsg_proto_verdict))) ||
-         (d_send_key && !in_alloc(d_send_key, uint64_t(n_streams) * 4)) || !in_alloc(d_reply, reply_cap) ||
-         !in_alloc(d_reply_off, (uint64_t(n) + 1) * 8) || !in_alloc(d_stream_reply, (uint64_t(n_streams) + 1) * 8) ||
-         !in_alloc(d_close_off, uint64_t(n_streams) * 8) ||
-         !in_alloc(d_verdict, uint64_t(n_streams) * sizeof(wsg_proto_verdict)) || !in_alloc(d_result, 3 * 8) ||
-         !in_alloc(d_msgs, uint64_t(n) * sizeof(wsg_msg)) || !in_alloc(d_count, 5 * 8) ||
-         !in_alloc(d_info, uint64_t(n) * sizeof(wsg_recv_info))))
-        return WSG_EINVAL;
-    hipStream_t s = as_stream(stream);
-    // both scratches are the context's: behind the last user of either,
-    // whatever stream it ran on
-    wsg::ProtoPlan pplan;
-    wsg::MsgPlans plan;
-    uint64_t pieces_cap;
-    bool ordered = false, pordered = false;
-    wsg::Utf8Inside utf8{which, d_valid, d_utf8_result, nullptr, 1, 1};
-    if (int rc = proto_scratch(c, s, n, n_streams, &pplan, &pordered, validated ? &utf8.also : nullptr))
-        return rc;
-    if (int rc = msg_scratch(c, s, n, wire_len, &plan, &pieces_cap, &ordered))
-        return rc;
-    wsg::RelayPlan rplan;
-    if (relay)
-        if (int rc = relay_scratch(c, n, n_streams, pieces_cap, &rplan))
-            return rc;
-    utf8.rec_grid = grid_for(c, ceil_div(n, wsg::BLOCK));
-    utf8.wire_grid = utf8_wire_grid(c, pieces_cap);
-    WSG_HIP(wsg::launch_reply_checked_plan(s, grid_for(c, ceil_div(n_streams, wsg::BLOCK)), d_wire, wire_len,
-                                           d_frame_start, n, d_stream_first, n_streams, d_state, d_proto, role,
-                                           max_message, d_also, make_rule(reply_op, mask), d_send_key, d_reply,
-                                           reply_cap, d_reply_off, d_stream_reply, d_close_off, d_verdict, d_result,
-                                           d_msgs, d_count, d_info, plan, pplan, c->d_msg_pieces, pieces_cap,
-                                           c->d_err, validated ? &utf8 : nullptr));
-    if (n)
-        if (int rc = gather_launch(c, s, wsg::launch_reply_gather, d_wire, plan.ref, pieces_cap, d_reply, reply_cap))
-            return rc;
-    if (relay) {
-        // behind the whole reply side, which it reads (d_info, d_msgs, d_verdict) and leaves as it is
-        wsg::ReplyRule rrule = make_rule(relay->relay_op, 0);
-        WSG_HIP(wsg::launch_relay_plan(s, d_info, n, n_streams, d_msgs, d_verdict, plan, rrule, relay->d_order,
-                                       relay->d_group_first, relay->n_groups, relay->d_relay, relay->relay_cap,
-                                       relay->d_relay_off, relay->d_group_relay, d_count, rplan, c->d_relay_pieces,
-                                       pieces_cap, c->d_err));
-        if (n && relays) {
-            const int t = timing_begin(c, s);
-            WSG_HIP(wsg::launch_relay_gather(s, grid_for(c, ceil_div(pieces_cap, wsg::BLOCK / 64), c->enc_blocks_per_cu),
-                                             d_wire, rplan, c->d_relay_pieces, pieces_cap, relay->d_relay,
-                                             relay->relay_cap));
-            timing_end(c, s, t);
-        }
-    }
-    if (int rc = scratch_leave(c->proto_order, s, pordered))
-        return rc;
-    return scratch_leave(c->msg_order, s, ordered);
-}
-
-} // namespace
 
 int wsg_reply_checked(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, const uint64_t* d_frame_start, uint32_t n,
                       const uint32_t* d_stream_first, uint32_t n_streams, wsg_stream_state* d_state,
@@ -652,10 +482,10 @@ int wsg_reply_checked(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, cons
                       wsg_proto_verdict* d_verdict, uint64_t* d_result, wsg_msg* d_msgs, uint64_t* d_count,
                       wsg_recv_info* d_info, void* stream)
 {
-    return reply_checked(c, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams, d_state, d_proto, role,
-                         max_message, d_also, reply_op, mask, d_send_key, d_reply, reply_cap, d_reply_off,
-                         d_stream_reply, d_close_off, d_verdict, d_result, d_msgs, d_count, d_info, stream, false, 0,
-                         nullptr, nullptr);
+    const wsg::Batch b{d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams};
+    const wsg::ProtoOps p{d_proto, role, max_message, d_also, d_verdict, d_result};
+    const wsg::ReplyOut r{reply_op, mask, d_send_key, d_reply, reply_cap, d_reply_off, d_stream_reply, d_close_off};
+    return reply_checked(c, b, d_state, p, r, wsg::MsgOut{d_msgs, d_count, d_info}, nullptr, nullptr, stream);
 }
 
 // wsg_reply_checked with wsg_check_utf8_wire and wsg_utf8_verdicts inside its
@@ -670,10 +500,11 @@ int wsg_reply_validated(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, co
                         uint64_t* d_utf8_result, wsg_msg* d_msgs, uint64_t* d_count, wsg_recv_info* d_info,
                         void* stream)
 {
-    return reply_checked(c, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams, d_state, d_proto, role,
-                         max_message, d_also, reply_op, mask, d_send_key, d_reply, reply_cap, d_reply_off,
-                         d_stream_reply, d_close_off, d_verdict, d_result, d_msgs, d_count, d_info, stream, true, which,
-                         d_valid, d_utf8_result);
+    const wsg::Batch b{d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams};
+    const wsg::ProtoOps p{d_proto, role, max_message, d_also, d_verdict, d_result};
+    const wsg::ReplyOut r{reply_op, mask, d_send_key, d_reply, reply_cap, d_reply_off, d_stream_reply, d_close_off};
+    const wsg::Utf8Inside u{which, d_valid, d_utf8_result, /*also*/ nullptr, /*grids*/ 1, 1};
+    return reply_checked(c, b, d_state, p, r, wsg::MsgOut{d_msgs, d_count, d_info}, &u, nullptr, stream);
 }
 
 int wsg_reply_checked_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_stream_span* d_span,
@@ -684,24 +515,11 @@ int wsg_reply_checked_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_l
                               uint64_t* d_close_off, wsg_proto_verdict* d_verdict, uint64_t* d_result, wsg_msg* d_msgs,
                               uint64_t* d_count, wsg_recv_info* d_info, uint32_t* n_frames_out, void* stream)
 {
-    if (!c || !n_frames_out || !d_count || !reply_op || !d_reply_off || !d_stream_reply || !d_close_off || !d_proto ||
-        !d_verdict || !d_result || (n_streams && !d_state) || (reply_cap && !d_reply) ||
-        (frame_cap && (!d_msgs || !d_info)) || !aligned16(d_reply) || role > WSG_PROTO_CLIENT)
-        return WSG_EINVAL;
-    if (c->check &&
-        (!in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) || !in_alloc(d_reply, reply_cap) ||
-         !in_alloc(d_reply_off, (uint64_t(frame_cap) + 1) * 8) ||
-         !in_alloc(d_msgs, uint64_t(frame_cap) * sizeof(wsg_msg)) ||
-         !in_alloc(d_info, uint64_t(frame_cap) * sizeof(wsg_recv_info))))
-        return WSG_EINVAL;
-    return streams_then(c, d_wire, wire_len, d_span, n_streams, d_state, d_frame_start, frame_cap, d_stream_first,
-                        d_count, n_frames_out, stream, [&](uint32_t n) {
-                            return wsg_reply_checked(c, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams,
-                                                     d_state, d_proto, role, max_message, nullptr, reply_op, mask,
-                                                     d_send_key, d_reply, reply_cap, d_reply_off, d_stream_reply,
-                                                     d_close_off, d_verdict, d_result, d_msgs, d_count, d_info,
-                                                     stream);
-                        });
+    const wsg::Framed f{d_span, d_frame_start, frame_cap, d_stream_first, n_frames_out};
+    const wsg::ProtoOps p{d_proto, role, max_message, /*also*/ nullptr, d_verdict, d_result};
+    const wsg::ReplyOut r{reply_op, mask, d_send_key, d_reply, reply_cap, d_reply_off, d_stream_reply, d_close_off};
+    return reply_streams(c, d_wire, wire_len, n_streams, f, d_state, &p, r, wsg::MsgOut{d_msgs, d_count, d_info},
+                         nullptr, nullptr, stream);
 }
 
 int wsg_reply_validated_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_stream_span* d_span,
@@ -714,24 +532,12 @@ int wsg_reply_validated_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire
                                 uint64_t* d_utf8_result, wsg_msg* d_msgs, uint64_t* d_count, wsg_recv_info* d_info,
                                 uint32_t* n_frames_out, void* stream)
 {
-    if (!c || !n_frames_out || !d_count || !reply_op || !d_reply_off || !d_stream_reply || !d_close_off || !d_proto ||
-        !d_verdict || !d_result || !d_utf8_result || (n_streams && !d_state) || (reply_cap && !d_reply) ||
-        (frame_cap && (!d_msgs || !d_info || !d_valid)) || !aligned16(d_reply) || role > WSG_PROTO_CLIENT)
-        return WSG_EINVAL;
-    if (c->check &&
-        (!in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) || !in_alloc(d_reply, reply_cap) ||
-         !in_alloc(d_reply_off, (uint64_t(frame_cap) + 1) * 8) ||
-         !in_alloc(d_msgs, uint64_t(frame_cap) * sizeof(wsg_msg)) || !in_alloc(d_valid, uint64_t(frame_cap) * 8) ||
-         !in_alloc(d_info, uint64_t(frame_cap) * sizeof(wsg_recv_info))))
-        return WSG_EINVAL;
-    return streams_then(c, d_wire, wire_len, d_span, n_streams, d_state, d_frame_start, frame_cap, d_stream_first,
-                        d_count, n_frames_out, stream, [&](uint32_t n) {
-                            return wsg_reply_validated(c, d_wire, wire_len, d_frame_start, n, d_stream_first,
-                                                       n_streams, d_state, d_proto, role, max_message, nullptr, which,
-                                                       reply_op, mask, d_send_key, d_reply, reply_cap, d_reply_off,
-                                                       d_stream_reply, d_close_off, d_verdict, d_result, d_valid,
-                                                       d_utf8_result, d_msgs, d_count, d_info, stream);
-                        });
+    const wsg::Framed f{d_span, d_frame_start, frame_cap, d_stream_first, n_frames_out};
+    const wsg::ProtoOps p{d_proto, role, max_message, /*also*/ nullptr, d_verdict, d_result};
+    const wsg::ReplyOut r{reply_op, mask, d_send_key, d_reply, reply_cap, d_reply_off, d_stream_reply, d_close_off};
+    const wsg::Utf8Inside u{which, d_valid, d_utf8_result, /*also*/ nullptr, /*grids*/ 1, 1};
+    return reply_streams(c, d_wire, wire_len, n_streams, f, d_state, &p, r, wsg::MsgOut{d_msgs, d_count, d_info}, &u,
+                         nullptr, stream);
 }
 
 // wsg_reply_validated with the relay's plan and gather behind it: the reply
@@ -748,11 +554,12 @@ int wsg_relay_validated(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, co
                         uint64_t* d_result, uint64_t* d_valid, uint64_t* d_utf8_result, wsg_msg* d_msgs,
                         uint64_t* d_count, wsg_recv_info* d_info, void* stream)
 {
-    const RelayArgs relay{relay_op, d_order, d_group_first, n_groups, d_relay, relay_cap, d_relay_off, d_group_relay};
-    return reply_checked(c, d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams, d_state, d_proto, role,
-                         max_message, d_also, reply_op, mask, d_send_key, d_reply, reply_cap, d_reply_off,
-                         d_stream_reply, d_close_off, d_verdict, d_result, d_msgs, d_count, d_info, stream, true, which,
-                         d_valid, d_utf8_result, &relay);
+    const wsg::Batch b{d_wire, wire_len, d_frame_start, n, d_stream_first, n_streams};
+    const wsg::ProtoOps p{d_proto, role, max_message, d_also, d_verdict, d_result};
+    const wsg::ReplyOut r{reply_op, mask, d_send_key, d_reply, reply_cap, d_reply_off, d_stream_reply, d_close_off};
+    const wsg::Utf8Inside u{which, d_valid, d_utf8_result, /*also*/ nullptr, /*grids*/ 1, 1};
+    const wsg::RelayArgs relay{relay_op, d_order, d_group_first, n_groups, d_relay, relay_cap, d_relay_off, d_group_relay};
+    return reply_checked(c, b, d_state, p, r, wsg::MsgOut{d_msgs, d_count, d_info}, &u, &relay, stream);
 }
 
 int wsg_relay_validated_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_stream_span* d_span,
@@ -767,32 +574,13 @@ int wsg_relay_validated_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire
                                 uint64_t* d_valid, uint64_t* d_utf8_result, wsg_msg* d_msgs, uint64_t* d_count,
                                 wsg_recv_info* d_info, uint32_t* n_frames_out, void* stream)
 {
-    if (!c || !n_frames_out || !d_count || !reply_op || !relay_op || !d_reply_off || !d_stream_reply || !d_close_off ||
-        !d_proto || !d_verdict || !d_result || !d_utf8_result || !d_group_relay || (n_streams && !d_state) ||
-        (reply_cap && !d_reply) || (relay_cap && !d_relay) ||
-        (frame_cap && (!d_msgs || !d_info || !d_valid || !d_relay_off)) || !aligned16(d_reply) ||
-        !aligned16(d_relay) || role > WSG_PROTO_CLIENT)
-        return WSG_EINVAL;
-    for (int k = 0; k < 5; ++k)
-        if (relay_op[k] && reply_op[k])
-            return WSG_EINVAL;
-    if (c->check &&
-        (!in_alloc(d_state, uint64_t(n_streams) * sizeof(wsg_stream_state)) || !in_alloc(d_reply, reply_cap) ||
-         !in_alloc(d_reply_off, (uint64_t(frame_cap) + 1) * 8) ||
-         !in_alloc(d_msgs, uint64_t(frame_cap) * sizeof(wsg_msg)) || !in_alloc(d_valid, uint64_t(frame_cap) * 8) ||
-         !in_alloc(d_relay_off, uint64_t(frame_cap) * 8) ||
-         !in_alloc(d_info, uint64_t(frame_cap) * sizeof(wsg_recv_info))))
-        return WSG_EINVAL;
-    return streams_then(c, d_wire, wire_len, d_span, n_streams, d_state, d_frame_start, frame_cap, d_stream_first,
-                        d_count, n_frames_out, stream, [&](uint32_t n) {
-                            return wsg_relay_validated(c, d_wire, wire_len, d_frame_start, n, d_stream_first,
-                                                       n_streams, d_state, d_proto, role, max_message, nullptr, which,
-                                                       reply_op, mask, d_send_key, relay_op, d_order, d_group_first,
-                                                       n_groups, d_reply, reply_cap, d_reply_off, d_stream_reply,
-                                                       d_close_off, d_relay, relay_cap, d_relay_off, d_group_relay,
-                                                       d_verdict, d_result, d_valid, d_utf8_result, d_msgs, d_count,
-                                                       d_info, stream);
-                        });
+    const wsg::Framed f{d_span, d_frame_start, frame_cap, d_stream_first, n_frames_out};
+    const wsg::ProtoOps p{d_proto, role, max_message, /*also*/ nullptr, d_verdict, d_result};
+    const wsg::ReplyOut r{reply_op, mask, d_send_key, d_reply, reply_cap, d_reply_off, d_stream_reply, d_close_off};
+    const wsg::Utf8Inside u{which, d_valid, d_utf8_result, /*also*/ nullptr, /*grids*/ 1, 1};
+    const wsg::RelayArgs relay{relay_op, d_order, d_group_first, n_groups, d_relay, relay_cap, d_relay_off, d_group_relay};
+    return reply_streams(c, d_wire, wire_len, n_streams, f, d_state, &p, r, wsg::MsgOut{d_msgs, d_count, d_info}, &u,
+                         &relay, stream);
 }
 
 // wsg_check_utf8's d_valid as the d_also of wsg_reply_checked: a seed per
@@ -800,13 +588,7 @@ int wsg_relay_validated_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire
 int wsg_utf8_verdicts(wsg_ctx* c, const wsg_msg* d_msgs, const uint64_t* d_count, uint32_t msg_room, uint32_t which,
                       const uint64_t* d_valid, uint32_t n_streams, wsg_proto_verdict* d_also, void* stream)
 {
-    if (!c || !d_count || (msg_room && (!d_msgs || !d_valid)) || (n_streams && !d_also) || n_streams == UINT32_MAX)
-        return WSG_EINVAL;
-    if (!aligned8(d_msgs) || !aligned8(d_count) || !aligned8(d_valid) || !aligned8(d_also))
-        return WSG_EINVAL;
-    if (c->check && (!in_alloc(d_msgs, uint64_t(msg_room) * sizeof(wsg_msg)) ||
-                     !in_alloc(d_valid, uint64_t(msg_room) * 8) || !in_alloc(d_count, 2 * 8) ||
-                     !in_alloc(d_also, uint64_t(n_streams) * sizeof(wsg_proto_verdict))))
+    if (!c || wsg::args_utf8_verdicts(d_msgs, d_count, msg_room, d_valid, n_streams, d_also, c->check))
         return WSG_EINVAL;
     if (n_streams == 0)
         return WSG_OK;
@@ -860,7 +642,7 @@ int encode_launch(wsg_ctx* c, hipStream_t s, const uint8_t* d_payload, const wsg
     const int t = timing_begin(c, s);
     for (uint64_t q0 = 0; q0 < pieces_cap; q0 += per) {
         const uint64_t q1 = std::min<uint64_t>(pieces_cap, q0 + per);
-        WSG_HIP(wsg::launch_encode_mask(s, grid_for(c, ceil_div(q1 - q0, wsg::BLOCK / 64), c->enc_blocks_per_cu),
+        WSG_HIP(wsg::launch_encode_mask(s, piece_grid(c, q1 - q0, c->enc_blocks_per_cu),
                                         d_payload, d_desc, n, d_wire_off, e.d_piece_start, e.d_piece_frame, d_wire,
                                         wire_cap, uint32_t(q0), uint32_t(q1)));
     }
@@ -871,19 +653,14 @@ int encode_launch(wsg_ctx* c, hipStream_t s, const uint8_t* d_payload, const wsg
 int wsg_encode_batch(wsg_ctx* c, const uint8_t* d_payload, const wsg_send_desc* d_desc, uint32_t n, uint8_t* d_wire,
                      uint64_t wire_cap, uint64_t* d_wire_off, void* stream)
 {
-    if (!c || !d_wire_off || (n && (!d_desc || !d_wire)))
-        return WSG_EINVAL;
-    if (!aligned16(d_wire))
+    if (!c || wsg::args_encode_batch(d_desc, n, d_wire, wire_cap, d_wire_off, c->check))
         return WSG_EINVAL;
     hipStream_t s = as_stream(stream);
     if (n == 0) {
         WSG_HIP(hipMemsetAsync(d_wire_off, 0, sizeof(uint64_t), s));
         return WSG_OK;
     }
-    if (c->check) {   // the descriptors come to the host: every payload range and the wire capacity
-        if (!in_alloc(d_desc, uint64_t(n) * sizeof(wsg_send_desc)) || !in_alloc(d_wire, wire_cap) ||
-            !in_alloc(d_wire_off, (uint64_t(n) + 1) * 8))
-            return WSG_EINVAL;
+    if (c->check) {   // the descriptors come to the host: every payload range
         std::vector<wsg_send_desc> h;
         try {
             h.resize(n);
@@ -971,16 +748,14 @@ int fanout_many(wsg_ctx* c, hipStream_t s, const uint8_t* d_payload, const uint6
 int wsg_fanout_encode(wsg_ctx* c, const uint8_t* d_payload, uint64_t len, const uint32_t* d_keys, uint32_t k,
                       uint8_t opcode, int mask, uint8_t* d_wire, uint64_t wire_cap, void* stream)
 {
-    if (!c || (k && (!d_keys || !d_wire)) || (len && !d_payload))
-        return WSG_EINVAL;
-    if (!aligned16(d_wire))
+    const uint64_t total = wsg_frame_size(opcode, mask, len, 0) * k;
+    if (!c || wsg::args_fanout_encode(d_payload, len, d_keys, k, d_wire, total, false))
         return WSG_EINVAL;
     if (k == 0)
         return WSG_OK;
-    const uint64_t total = wsg_frame_size(opcode, mask, len, 0) * k;
     if (total > wire_cap)
         return WSG_ENOMEM;
-    if (c->check && (!in_alloc(d_payload, len) || !in_alloc(d_keys, uint64_t(k) * 4) || !in_alloc(d_wire, total)))
+    if (c->check && wsg::args_fanout_encode(d_payload, len, d_keys, k, d_wire, total, true))
         return WSG_EINVAL;
     hipStream_t s = as_stream(stream);
     const uint64_t src = 0, off[2] = {0, total};
@@ -996,9 +771,7 @@ int wsg_fanout_encode_many(wsg_ctx* c, const uint8_t* d_payload, const uint64_t*
                            uint8_t* d_wire, uint64_t wire_cap, uint64_t* wire_off, void* stream)
 {
     try {   // no C++ exception leaves the ABI (host vectors: WSG_ENOMEM)
-        if (!c || !wire_off || (m && (!src_off || !len || !opcode)) || (m && k && (!d_keys || !d_wire)))
-            return WSG_EINVAL;
-        if (d_wire && !aligned16(d_wire))
+        if (!c || wsg::args_fanout_encode_many(src_off, len, opcode, m, d_keys, k, d_wire, 0, wire_off, false))
             return WSG_EINVAL;
         // message i's frames from wire_off[i], line-aligned (whole-line store rows)
         uint64_t at = 0;
@@ -1017,7 +790,7 @@ int wsg_fanout_encode_many(wsg_ctx* c, const uint8_t* d_payload, const uint64_t*
         if (any_payload && !d_payload)
             return WSG_EINVAL;
         if (c->check) {
-            if (!in_alloc(d_keys, uint64_t(k) * 4) || !in_alloc(d_wire, at))
+            if (wsg::args_fanout_encode_many(src_off, len, opcode, m, d_keys, k, d_wire, at, wire_off, true))
                 return WSG_EINVAL;
             for (uint32_t i = 0; i < m; ++i)
                 if (len[i] && !in_alloc(d_payload + src_off[i], len[i]))

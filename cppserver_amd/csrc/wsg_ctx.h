@@ -187,10 +187,11 @@ struct wsg_ctx {
 // Everything below is the library's own: none of it is exported.
 #pragma GCC visibility push(hidden)
 
+#include "wsg_args.h"   // the entry points' argument checks (declares in_alloc)
+
 constexpr unsigned long long kNoError = ~0ull;
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 // The `stream` argument of an entry point: NULL selects HIP's default (null)
 // stream, as in every HIP API.
 inline hipStream_t as_stream(void* s) { return static_cast<hipStream_t>(s); }
@@ -272,12 +273,12 @@ int scratch_enter(wsg_scratch_order& o, hipStream_t s, bool* ordered);
 // Behind the call's last launch on `s`.
 int scratch_leave(wsg_scratch_order& o, hipStream_t s, bool ordered);
 void free_enc(wsg_enc_scratch& e);
-// Checked launches ($WSG_CHECK=1, a debug mode): [p, p + bytes) must lie in
-// ONE device allocation (hipMemGetAddressRange), which every access of the
-// kernel to that operand stays inside when the sizes passed are right.  GPU
-// address sanitizers are not available on the target pool; this catches a
-// short buffer or a wrong size on the host, before the kernel runs.
-bool in_alloc(const void* p, uint64_t bytes);
+// in_alloc (declared in wsg_args.h, whose rows ask it).  Checked launches
+// ($WSG_CHECK=1, a debug mode): [p, p + bytes) must lie in ONE device
+// allocation (hipMemGetAddressRange), which every access of the kernel to that
+// operand stays inside when the sizes passed are right.  GPU address
+// sanitizers are not available on the target pool; this catches a short
+// buffer or a wrong size on the host, before the kernel runs.
 
 // ---- wsg_capi_device.cpp -----------------------------------------------------
 // Device decode: one k_decode launch (the pipelined host path runs several

@@ -2,10 +2,13 @@
 // kernel sources (wsg_decode.hip, wsg_encode.hip, wsg_fanout.hip,
 // wsg_lane_device.hip, wsg_misc.hip, wsg_messages.hip, wsg_frames.hip,
 // wsg_utf8.hip, wsg_proto.hip, wsg_assembly.hip, wsg_upgrade.hip, wsg_carry.hip, wsg_relay.hip) and the C-ABI implementation (wsg_ctx.h).
+// The launchers take the operand groups of wsg_operands.h by const reference
+// and unpack them at the <<<>>> call: no kernel sees a group.
 #pragma once
 
 #include "wsg_frame.h"
 #include "wsg_lane_plan.h"   // LANE_THREADS, LANE_GROUPS_MAX
+#include "wsg_operands.h"    // the operand groups the launchers take: Batch, MsgOut, ReplyOut, ProtoOps, ...
 
 namespace wsg {
 
@@ -169,32 +172,34 @@ struct alignas(32) MsgPiece {
     uint32_t key;
     uint32_t k;      // piece of the frame: [A + k * PIECE, A + (k + 1) * PIECE) of d_msg, A = d0 & ~(PIECE_ALIGN - 1)
 };
+// The scratch of a call that runs the message plan, and its error latch: what
+// the entry points' msg_scratch() fills.
+struct MsgScratch {
+    MsgPlans plans;
+    MsgPiece* pieces;
+    uint64_t pieces_cap;
+    unsigned long long* err;
+};
 // The plan pass: d_info, d_msgs, d_count, d_state, the plan and the piece
 // records (pieces_cap entries); latches frame errors and WSG_ENOMEM.
-hipError_t launch_msg_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
-                           const uint32_t* stream_first, uint32_t n_streams, wsg_stream_state* state, uint64_t msg_cap,
-                           wsg_msg* msgs, uint64_t* count, wsg_recv_info* info, const MsgPlans& plans,
-                           MsgPiece* pieces, uint64_t pieces_cap, unsigned long long* err);
-// The gather pass: every delivered payload byte, unmasked, to its place in msg.
-hipError_t launch_msg_gather(hipStream_t s, int grid, const uint8_t* wire, const MsgPlan& plan,
-                             const MsgPiece* pieces, uint64_t pieces_cap, uint8_t* msg, uint64_t msg_cap);
+// state null (wsg_check_utf8_wire, with msg_cap UINT64_MAX): d_state is only
+// read, as `seed` (the sticky opcodes), and k_msg_state is left out; else seed is state.
+hipError_t launch_msg_plan(hipStream_t s, const Batch& b, wsg_stream_state* state, const wsg_stream_state* seed,
+                           uint64_t msg_cap, const MsgOut& o, const MsgScratch& x);
+// The gather pass over piece records, a wave per piece: every payload byte of
+// the pieces below tot[3] to its place in dst.  tot: MsgPlan::tot (the
+// delivered payloads, unmasked, to d_msg), MsgPlan::rtot (a reply's, re-keyed,
+// to the reply wire) or RelayPlan::gtot (the relayed ones, unmasked, to d_relay).
+hipError_t launch_gather(hipStream_t s, int grid, const uint8_t* wire, const uint64_t* tot, const MsgPiece* pieces,
+                         uint64_t pieces_cap, uint8_t* dst, uint64_t dst_cap);
 
 // ---- replies (wsg_reply_messages; wsg_messages.hip) -------------------------
-// The caller's rule, by value in the kernels' arguments.
-struct ReplyRule {
-    uint8_t op[5];   // by WSG_CB_*: the reply's first header byte, 0 (none) or WSG_REPLY_SAME
-    uint8_t mask;
-};
 // The plan pass of a reply: launch_msg_plan's outputs but the d_msg layout's
 // capacity check, and d_reply_off, d_stream_reply, d_count[2..3], every reply
 // frame's header and status prefix, and piece records whose destination is
 // the reply wire; latches frame errors and WSG_ENOMEM (reply_cap).
-hipError_t launch_reply_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
-                             const uint32_t* stream_first, uint32_t n_streams, wsg_stream_state* state,
-                             const ReplyRule& rule, const uint32_t* send_key, uint8_t* reply, uint64_t reply_cap,
-                             uint64_t* reply_off, uint64_t* stream_reply, wsg_msg* msgs, uint64_t* count,
-                             wsg_recv_info* info, const MsgPlans& plans, MsgPiece* pieces, uint64_t pieces_cap,
-                             unsigned long long* err);
+hipError_t launch_reply_plan(hipStream_t s, const Batch& b, wsg_stream_state* state, const ReplyOut& r,
+                             const MsgOut& o, const MsgScratch& x);
 // wsg_reply_checked's plan pass: launch_reply_plan with the protocol kernels
 // (launch_proto_* below, d_state's consumed written ahead of them) and the
 // merge with `also` (or null) between the message plan and the reply kernels,
@@ -202,21 +207,11 @@ hipError_t launch_reply_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_l
 // frame and put its close frame there; d_close_off, d_verdict, d_proto,
 // d_result and d_count[0..5) besides launch_reply_plan's outputs.
 // stream_grid: blocks of the per-stream kernels (grid-stride).
+// utf8 (wsg_reply_validated, or null): Utf8Inside of wsg_operands.h.
 struct ProtoPlan;
-struct Utf8Inside;   // below, with the UTF-8 launchers
-hipError_t launch_reply_checked_plan(hipStream_t s, int stream_grid, const uint8_t* wire, uint64_t wire_len,
-                                     const uint64_t* fs, uint32_t n, const uint32_t* stream_first, uint32_t n_streams,
-                                     wsg_stream_state* state, wsg_proto_state* proto, uint32_t role,
-                                     uint64_t max_message, const wsg_proto_verdict* also, const ReplyRule& rule,
-                                     const uint32_t* send_key, uint8_t* reply, uint64_t reply_cap, uint64_t* reply_off,
-                                     uint64_t* stream_reply, uint64_t* close_off, wsg_proto_verdict* verdict,
-                                     uint64_t* result, wsg_msg* msgs, uint64_t* count, wsg_recv_info* info,
-                                     const MsgPlans& plans, const ProtoPlan& pplan, MsgPiece* pieces,
-                                     uint64_t pieces_cap, unsigned long long* err,
-                                     const Utf8Inside* utf8 = nullptr);
-// k_msg_gather over those records: every replied payload byte, re-keyed, to its place in reply.
-hipError_t launch_reply_gather(hipStream_t s, int grid, const uint8_t* wire, const MsgPlan& plan,
-                               const MsgPiece* pieces, uint64_t pieces_cap, uint8_t* reply, uint64_t reply_cap);
+hipError_t launch_reply_checked_plan(hipStream_t s, int stream_grid, const Batch& b, wsg_stream_state* state,
+                                     const ProtoOps& p, const ProtoPlan& pplan, const ReplyOut& r, const MsgOut& o,
+                                     const MsgScratch& x, const Utf8Inside* utf8 = nullptr);
 
 // ---- relays (wsg_relay_validated; wsg_relay.hip) -----------------------------
 // Scratch of one call, carved by the host out of one device block
@@ -255,44 +250,29 @@ uint64_t relay_plan_layout(uint8_t* base, uint32_t n, uint32_t ns, RelayPlan* pl
 // and status prefix and the piece records of the relayed frames, whose
 // destination is d_relay and whose key is the receive key; latches WSG_EINVAL
 // (order, group_first; index n + 1 + the plan's `bad`) and WSG_ENOMEM
-// (relay_cap; index n + 1).  A relay frame is unmasked: the launcher clears rule.mask, whatever the
-// caller's rule holds, before the kernels size a frame with it.
-hipError_t launch_relay_plan(hipStream_t s, const wsg_recv_info* info, uint32_t n, uint32_t n_streams,
-                             const wsg_msg* msgs, const wsg_proto_verdict* verdict, const MsgPlans& plans,
-                             const ReplyRule& rule, const uint32_t* order, const uint32_t* group_first,
-                             uint32_t n_groups, uint8_t* relay, uint64_t relay_cap, uint64_t* relay_off,
-                             uint64_t* group_relay, uint64_t* count, const RelayPlan& Q, MsgPiece* pieces,
-                             uint64_t pieces_cap, unsigned long long* err);
-// k_msg_gather over those records: every relayed payload byte, unmasked, to its place in relay.
-hipError_t launch_relay_gather(hipStream_t s, int grid, const uint8_t* wire, const RelayPlan& Q,
-                               const MsgPiece* pieces, uint64_t pieces_cap, uint8_t* relay, uint64_t relay_cap);
+// (relay_cap; index n + 1).  A relay frame is unmasked: the kernels size it by relay.relay_op and
+// no mask.  x: the message plan's as it stands, with the relay's own piece records.
+hipError_t launch_relay_plan(hipStream_t s, const Batch& b, const MsgOut& o, const wsg_proto_verdict* verdict,
+                             const RelayArgs& relay, const RelayPlan& Q, const MsgScratch& x);
 
 // ---- WSG_ASSEMBLY_RFC (wsg_set_assembly; wsg_assembly.hip) ------------------
 // The plan kernels of RFC 6455 5.4's rule, in the places the launchers of
 // wsg_messages.hip run the reference rule's (n > 0 but for launch_rfc_state).
 // The four scan kernels: d_info and the error latch, P.sidx, R, P.tot,
 // d_count[0..1], WSG_ENOMEM (msg_cap); d_state[j].ahead is read.
-hipError_t launch_rfc_scans(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
-                            const uint32_t* stream_first, uint32_t n_streams, const wsg_stream_state* state,
-                            uint64_t msg_cap, uint64_t* count, wsg_recv_info* info, const MsgPlan& P, const RfcPlan& R,
-                            unsigned long long* err);
+hipError_t launch_rfc_scans(hipStream_t s, const Batch& b, const wsg_stream_state* state, uint64_t msg_cap,
+                            const MsgOut& o, const MsgScratch& x);
 // k_msg_finalize's part: d_msgs and the gather's piece records, in dense order.
-hipError_t launch_rfc_finalize(hipStream_t s, const uint8_t* wire, const wsg_recv_info* info, uint32_t n,
-                               const MsgPlan& P, const RfcPlan& R, wsg_msg* msgs, MsgPiece* pieces,
-                               uint64_t pieces_cap);
+hipError_t launch_rfc_finalize(hipStream_t s, const Batch& b, const MsgOut& o, const MsgScratch& x);
 // k_msg_state's part (consumed, opcode 0, ahead), or k_msg_consumed's (consumed alone); n == 0 allowed.
 hipError_t launch_rfc_state(hipStream_t s, uint32_t n, const uint32_t* stream_first, uint32_t n_streams,
                             wsg_stream_state* state, const RfcPlan& R, bool consumed_only);
-// k_reply_local's and k_reply_finalize's parts, around k_reply_blocks.
-hipError_t launch_rfc_reply_local(hipStream_t s, bool checked, const uint8_t* wire, const wsg_recv_info* info,
-                                  uint32_t n, const MsgPlan& P, const RfcPlan& R, const ReplyRule& rule, wsg_msg* msgs,
-                                  const uint64_t* verdict);
-hipError_t launch_rfc_reply_finalize(hipStream_t s, bool checked, const wsg_recv_info* info, uint32_t n,
-                                     const uint32_t* stream_first, uint32_t n_streams, const MsgPlan& P,
-                                     const RfcPlan& R, const ReplyRule& rule, const uint32_t* send_key,
-                                     const wsg_msg* msgs, uint8_t* reply, uint64_t reply_cap, uint64_t* reply_off,
-                                     uint64_t* stream_reply, MsgPiece* pieces, uint64_t pieces_cap,
-                                     const uint64_t* verdict, uint64_t* close_off);
+// k_reply_local's and k_reply_finalize's parts, around k_reply_blocks
+// (verdict: d_verdict as words when checked, null and r.close_off null otherwise).
+hipError_t launch_rfc_reply_local(hipStream_t s, bool checked, const Batch& b, const MsgOut& o, const MsgScratch& x,
+                                  const ReplyRule& rule, const uint64_t* verdict);
+hipError_t launch_rfc_reply_finalize(hipStream_t s, bool checked, const Batch& b, const MsgOut& o, const MsgScratch& x,
+                                     const ReplyOut& r, const ReplyRule& rule, const uint64_t* verdict);
 
 // ---- the device framer (wsg_frame_streams; wsg_frames.hip) -----------------
 // Scratch of one call, carved out of one device array of uint64 (one block =
@@ -390,32 +370,14 @@ hipError_t launch_utf8_verdicts(hipStream_t s, int rec_grid, int stream_grid, co
 // d_valid as launch_utf8_scan leaves it for the dense layout of the same
 // messages.  Between launch_utf8_init and launch_utf8_count (msg_cap
 // UINT64_MAX: every record lies inside the layout).
-hipError_t launch_utf8_wire(hipStream_t s, int grid, const uint8_t* wire, uint64_t wire_len, const MsgPlan& plan,
-                            const MsgPiece* pieces, uint64_t pieces_cap, const wsg_msg* msgs, const uint64_t* count,
-                            uint32_t msg_room, uint32_t which, uint64_t* valid);
+// (msg_room is b.n: a message ends in a frame.)
+hipError_t launch_utf8_wire(hipStream_t s, int grid, const Batch& b, const MsgOut& o, const MsgScratch& x,
+                            uint32_t which, uint64_t* valid);
 // wsg_reply_validated: launch_utf8_verdicts over a seed that is also_in[j]
 // (null: none) where that names a frame of stream j, all 0xFF otherwise.
-hipError_t launch_utf8_verdicts_over(hipStream_t s, int rec_grid, int stream_grid, uint32_t n,
-                                     const uint32_t* stream_first, const wsg_proto_verdict* also_in,
-                                     const wsg_msg* msgs, const uint64_t* count, uint32_t msg_room, uint32_t which,
-                                     const uint64_t* valid, uint32_t n_streams, uint64_t* also);
-// wsg_check_utf8_wire's plan pass: launch_msg_plan with no capacity and
-// without k_msg_state, so d_state is read (the sticky-opcode seed) and not written.
-hipError_t launch_msg_plan_only(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
-                                const uint32_t* stream_first, uint32_t n_streams, const wsg_stream_state* state,
-                                wsg_msg* msgs, uint64_t* count, wsg_recv_info* info, const MsgPlans& plans,
-                                MsgPiece* pieces, uint64_t pieces_cap, unsigned long long* err);
-// What wsg_reply_validated adds to launch_reply_checked_plan: the UTF-8 check
-// from the wire between the protocol judge and the merge, on the dense piece
-// records of k_msg_finalize, and its verdicts merged with the caller's.
-struct Utf8Inside {
-    uint32_t which;
-    uint64_t* valid;     // n words
-    uint64_t* result;    // 4 words
-    uint64_t* also;      // n_streams words of scratch: the merged d_also
-    int rec_grid;        // blocks of the per-record kernels (at least one)
-    int wire_grid;       // blocks of k_utf8_wire
-};
+// (over the b.n records u.valid has; the merged verdicts into u.also)
+hipError_t launch_utf8_verdicts_over(hipStream_t s, int stream_grid, const Batch& b,
+                                     const wsg_proto_verdict* also_in, const MsgOut& o, const Utf8Inside& u);
 
 // ---- protocol rules on the device (wsg_check_protocol; wsg_proto.hip) -------
 struct ProtoStep;   // wsg_proto.h
@@ -432,23 +394,20 @@ uint64_t proto_plan_layout(uint8_t* base, uint32_t n, uint32_t ns, ProtoPlan* pl
 // k_proto_local and k_proto_blocks: d_verdict and d_result seeded (all 0xFF;
 // {0, UINT64_MAX, 0}), the frames' streams and the scanned block partials in
 // the plan.  At least one block, also for n == 0 or n_streams == 0.
-hipError_t launch_proto_scan(hipStream_t s, const wsg_recv_info* info, uint32_t n, const uint32_t* stream_first,
-                             uint32_t n_streams, const wsg_proto_state* proto, const ProtoPlan& plan,
-                             wsg_proto_verdict* verdict, uint64_t* result);
+// (The protocol launchers read b.n, b.stream_first, b.n_streams and, the judge, the wire; info: the decode's.)
+hipError_t launch_proto_scan(hipStream_t s, const Batch& b, const wsg_recv_info* info, const ProtoOps& p,
+                             const ProtoPlan& plan);
 // The per-frame judging kernel (n > 0 and n_streams > 0): every frame's code,
 // the first of each stream into d_verdict by atomicMin; the state d_proto asks
 // for into the plan.
-hipError_t launch_proto_judge(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const wsg_recv_info* info,
-                              uint32_t n, const uint32_t* stream_first, const wsg_stream_state* state,
-                              const wsg_proto_state* proto, uint32_t role, uint64_t max_message, const ProtoPlan& plan,
-                              wsg_proto_verdict* verdict);
+hipError_t launch_proto_judge(hipStream_t s, const Batch& b, const wsg_recv_info* info,
+                              const wsg_stream_state* state, const ProtoOps& p, const ProtoPlan& plan);
 // wsg_reply_checked: d_verdict[j] replaced by also[j] where that comes first (one lane per stream, grid-stride).
 hipError_t launch_proto_merge(hipStream_t s, int grid, uint32_t n, const uint32_t* stream_first, uint32_t n_streams,
                               const wsg_proto_verdict* also, wsg_proto_verdict* verdict);
 // One lane per stream (grid-stride): d_proto and d_result's counts.
-hipError_t launch_proto_finish(hipStream_t s, int grid, uint32_t n, const uint32_t* stream_first, uint32_t n_streams,
-                               const wsg_stream_state* state, wsg_proto_state* proto, const ProtoPlan& plan,
-                               const wsg_proto_verdict* verdict, uint64_t* result);
+hipError_t launch_proto_finish(hipStream_t s, int grid, const Batch& b, const wsg_stream_state* state,
+                               const ProtoOps& p, const ProtoPlan& plan);
 
 // ---- fan-out (wsg_fanout_encode, wsg_fanout_encode_many; wsg_fanout.hip) ----
 // Messages of one fan-out launch (blockIdx.y): payload and output offsets.

@@ -607,39 +607,38 @@ uint64_t msg_plan_layout(uint8_t* base, uint32_t n, MsgPlan* plan)
 // nothing consumed), the totals and count_words of d_count zeroed; k_msg_state
 // (launch_rfc_state) behind either when `state` is given.
 template <class Finish>
-static hipError_t launch_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
-                              const uint32_t* stream_first, uint32_t n_streams, wsg_stream_state* state,
-                              const wsg_stream_state* seed, uint64_t msg_cap, uint64_t* count, uint32_t count_words,
-                              wsg_recv_info* info, const MsgPlans& plans, unsigned long long* err, Finish finish)
+static hipError_t launch_plan(hipStream_t s, const Batch& b, wsg_stream_state* state, const wsg_stream_state* seed,
+                              uint64_t msg_cap, const MsgOut& o, uint32_t count_words, const MsgScratch& x,
+                              Finish finish)
 {
-    const MsgPlan& plan = plans.ref;
-    const bool rfc = plans.assembly == WSG_ASSEMBLY_RFC;
-    const uint32_t nb = uint32_t((uint64_t(n) + BLOCK - 1) / BLOCK);
+    const MsgPlan& plan = x.plans.ref;
+    const bool rfc = x.plans.assembly == WSG_ASSEMBLY_RFC;
+    const uint32_t nb = uint32_t((uint64_t(b.n) + BLOCK - 1) / BLOCK);
     hipError_t re = hipSuccess;   // of the other source's launchers (each has taken its launch's error)
-    if (n == 0) {
+    if (b.n == 0) {
         if (hipError_t e = hipMemsetAsync(plan.tot, 0, 4 * sizeof(uint64_t), s); e != hipSuccess)
             return e;
-        if (hipError_t e = hipMemsetAsync(count, 0, count_words * sizeof(uint64_t), s); e != hipSuccess)
+        if (hipError_t e = hipMemsetAsync(o.count, 0, count_words * sizeof(uint64_t), s); e != hipSuccess)
             return e;
     } else if (rfc) {
-        re = launch_rfc_scans(s, wire, wire_len, fs, n, stream_first, n_streams, seed, msg_cap, count, info, plan,
-                              plans.rfc, err);
+        re = launch_rfc_scans(s, b, seed, msg_cap, o, x);
         finish(nb);
     } else {
-        k_msg_scan_local<<<nb, BLOCK, 0, s>>>(wire, wire_len, fs, n, stream_first, n_streams, info, plan, err);
-        k_msg_scan_blocks<<<1, BLOCK, 0, s>>>(plan, nb, count);
-        k_msg_bytes_local<<<nb, BLOCK, 0, s>>>(info, n, stream_first, plan);
-        k_msg_bytes_blocks<<<1, BLOCK, 0, s>>>(plan, nb, n, msg_cap, count, err);
+        k_msg_scan_local<<<nb, BLOCK, 0, s>>>(b.wire, b.wire_len, b.fs, b.n, b.stream_first, b.n_streams, o.info, plan,
+                                              x.err);
+        k_msg_scan_blocks<<<1, BLOCK, 0, s>>>(plan, nb, o.count);
+        k_msg_bytes_local<<<nb, BLOCK, 0, s>>>(o.info, b.n, b.stream_first, plan);
+        k_msg_bytes_blocks<<<1, BLOCK, 0, s>>>(plan, nb, b.n, msg_cap, o.count, x.err);
         finish(nb);
     }
-    if (n_streams && state) {
+    if (b.n_streams && state) {
         if (rfc) {
-            if (hipError_t e = launch_rfc_state(s, n, stream_first, n_streams, state, plans.rfc, false);
+            if (hipError_t e = launch_rfc_state(s, b.n, b.stream_first, b.n_streams, state, x.plans.rfc, false);
                 re == hipSuccess)
                 re = e;
         } else {
-            k_msg_state<<<(n_streams + BLOCK - 1) / BLOCK, BLOCK, 0, s>>>(info, n, stream_first, n_streams, state,
-                                                                           plan);
+            k_msg_state<<<(b.n_streams + BLOCK - 1) / BLOCK, BLOCK, 0, s>>>(o.info, b.n, b.stream_first, b.n_streams,
+                                                                             state, plan);
         }
     }
     const hipError_t e = hipGetLastError();
@@ -647,180 +646,129 @@ static hipError_t launch_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_
 }
 
 // k_msg_finalize, or its part under WSG_ASSEMBLY_RFC.
-static hipError_t launch_finalize(hipStream_t s, uint32_t nb, const uint8_t* wire, const wsg_recv_info* info,
-                                  uint32_t n, const uint32_t* stream_first, const wsg_stream_state* state,
-                                  const MsgPlans& plans, wsg_msg* msgs, MsgPiece* pieces, uint64_t pieces_cap)
+static hipError_t launch_finalize(hipStream_t s, uint32_t nb, const Batch& b, const wsg_stream_state* state,
+                                  const MsgOut& o, const MsgScratch& x)
 {
-    if (plans.assembly == WSG_ASSEMBLY_RFC)
-        return launch_rfc_finalize(s, wire, info, n, plans.ref, plans.rfc, msgs, pieces, pieces_cap);
-    k_msg_finalize<<<nb, BLOCK, 0, s>>>(wire, info, n, stream_first, state, plans.ref, msgs, pieces, pieces_cap);
+    if (x.plans.assembly == WSG_ASSEMBLY_RFC)
+        return launch_rfc_finalize(s, b, o, x);
+    k_msg_finalize<<<nb, BLOCK, 0, s>>>(b.wire, o.info, b.n, b.stream_first, state, x.plans.ref, o.msgs, x.pieces,
+                                        x.pieces_cap);
     return hipGetLastError();
 }
 
-hipError_t launch_msg_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
-                           const uint32_t* stream_first, uint32_t n_streams, wsg_stream_state* state, uint64_t msg_cap,
-                           wsg_msg* msgs, uint64_t* count, wsg_recv_info* info, const MsgPlans& plans,
-                           MsgPiece* pieces, uint64_t pieces_cap, unsigned long long* err)
+hipError_t launch_msg_plan(hipStream_t s, const Batch& b, wsg_stream_state* state, const wsg_stream_state* seed,
+                           uint64_t msg_cap, const MsgOut& o, const MsgScratch& x)
 {
     hipError_t fe = hipSuccess;
-    const hipError_t e = launch_plan(s, wire, wire_len, fs, n, stream_first, n_streams, state, state, msg_cap, count, 2,
-                                     info, plans, err, [&](uint32_t nb) {
-                                         fe = launch_finalize(s, nb, wire, info, n, stream_first, state, plans, msgs,
-                                                              pieces, pieces_cap);
-                                     });
+    const hipError_t e = launch_plan(s, b, state, seed, msg_cap, o, 2, x,
+                                     [&](uint32_t nb) { fe = launch_finalize(s, nb, b, seed, o, x); });
     return fe != hipSuccess ? fe : e;
 }
 
-// (d_state is only read: the plan takes its seed from it, k_msg_state is left out)
-hipError_t launch_msg_plan_only(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
-                                const uint32_t* stream_first, uint32_t n_streams, const wsg_stream_state* state,
-                                wsg_msg* msgs, uint64_t* count, wsg_recv_info* info, const MsgPlans& plans,
-                                MsgPiece* pieces, uint64_t pieces_cap, unsigned long long* err)
+hipError_t launch_gather(hipStream_t s, int grid, const uint8_t* wire, const uint64_t* tot, const MsgPiece* pieces,
+                         uint64_t pieces_cap, uint8_t* dst, uint64_t dst_cap)
 {
-    hipError_t fe = hipSuccess;
-    const hipError_t e = launch_plan(s, wire, wire_len, fs, n, stream_first, n_streams, nullptr, state, UINT64_MAX,
-                                     count, 2, info, plans, err, [&](uint32_t nb) {
-                                         fe = launch_finalize(s, nb, wire, info, n, stream_first, state, plans, msgs,
-                                                              pieces, pieces_cap);
-                                     });
-    return fe != hipSuccess ? fe : e;
-}
-
-hipError_t launch_msg_gather(hipStream_t s, int grid, const uint8_t* wire, const MsgPlan& plan,
-                             const MsgPiece* pieces, uint64_t pieces_cap, uint8_t* msg, uint64_t msg_cap)
-{
-    k_msg_gather<<<grid, BLOCK, 0, s>>>(wire, plan.tot, pieces, pieces_cap, msg, msg_cap);
+    k_msg_gather<<<grid, BLOCK, 0, s>>>(wire, tot, pieces, pieces_cap, dst, dst_cap);
     return hipGetLastError();
 }
 
-hipError_t launch_reply_plan(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const uint64_t* fs, uint32_t n,
-                             const uint32_t* stream_first, uint32_t n_streams, wsg_stream_state* state,
-                             const ReplyRule& rule, const uint32_t* send_key, uint8_t* reply, uint64_t reply_cap,
-                             uint64_t* reply_off, uint64_t* stream_reply, wsg_msg* msgs, uint64_t* count,
-                             wsg_recv_info* info, const MsgPlans& plans, MsgPiece* pieces, uint64_t pieces_cap,
-                             unsigned long long* err)
+// A batch of no frame has no reply either: the totals, d_reply_off[0] and
+// d_stream_reply zeroed, and no stream closed (r.close_off, when checked).
+static hipError_t reply_of_none(hipStream_t s, uint32_t n_streams, const MsgPlan& plan, const ReplyOut& r)
 {
-    const MsgPlan& plan = plans.ref;
-    if (n == 0) {   // no reply either
-        if (hipError_t e = hipMemsetAsync(plan.rtot, 0, 4 * sizeof(uint64_t), s); e != hipSuccess)
-            return e;
-        if (hipError_t e = hipMemsetAsync(reply_off, 0, sizeof(uint64_t), s); e != hipSuccess)
-            return e;
-        if (hipError_t e = hipMemsetAsync(stream_reply, 0, (uint64_t(n_streams) + 1) * sizeof(uint64_t), s);
-            e != hipSuccess)
-            return e;
+    if (hipError_t e = hipMemsetAsync(plan.rtot, 0, 4 * sizeof(uint64_t), s); e != hipSuccess)
+        return e;
+    if (hipError_t e = hipMemsetAsync(r.reply_off, 0, sizeof(uint64_t), s); e != hipSuccess)
+        return e;
+    if (hipError_t e = hipMemsetAsync(r.stream_reply, 0, (uint64_t(n_streams) + 1) * sizeof(uint64_t), s);
+        e != hipSuccess)
+        return e;
+    if (r.close_off && n_streams)
+        return hipMemsetAsync(r.close_off, 0xFF, uint64_t(n_streams) * sizeof(uint64_t), s);
+    return hipSuccess;
+}
+
+// The reply kernels behind the message plan's scans (n > 0); v: d_verdict as
+// words when CHECKED, null otherwise.
+template <bool CHECKED>
+static hipError_t launch_reply_kernels(hipStream_t s, uint32_t nb, const Batch& b, const wsg_stream_state* state,
+                                       const ReplyOut& r, const MsgOut& o, const MsgScratch& x, const uint64_t* v)
+{
+    const MsgPlan& plan = x.plans.ref;
+    const ReplyRule rule = reply_rule(r.reply_op, r.mask);
+    if (x.plans.assembly == WSG_ASSEMBLY_RFC) {
+        const hipError_t e = launch_rfc_reply_local(s, CHECKED, b, o, x, rule, v);
+        k_reply_blocks<CHECKED><<<1, BLOCK, 0, s>>>(plan, nb, b.n, r.reply_cap, o.count, x.err);
+        const hipError_t f = launch_rfc_reply_finalize(s, CHECKED, b, o, x, r, rule, v);
+        return e != hipSuccess ? e : f;
     }
+    k_reply_local<CHECKED><<<nb, BLOCK, 0, s>>>(b.wire, o.info, b.n, b.stream_first, state, plan, rule, o.msgs, v);
+    k_reply_blocks<CHECKED><<<1, BLOCK, 0, s>>>(plan, nb, b.n, r.reply_cap, o.count, x.err);
+    k_reply_finalize<CHECKED><<<nb, BLOCK, 0, s>>>(o.info, b.n, b.stream_first, b.n_streams, plan, rule, r.send_key,
+                                                   o.msgs, r.reply, r.reply_cap, r.reply_off, r.stream_reply, x.pieces,
+                                                   x.pieces_cap, v, r.close_off);
+    return hipSuccess;   // (launch_plan takes the launches' error)
+}
+
+hipError_t launch_reply_plan(hipStream_t s, const Batch& b, wsg_stream_state* state, const ReplyOut& r,
+                             const MsgOut& o, const MsgScratch& x)
+{
+    if (b.n == 0)
+        if (hipError_t e = reply_of_none(s, b.n_streams, x.plans.ref, r); e != hipSuccess)
+            return e;
     hipError_t fe = hipSuccess;
-    const auto keep = [&fe](hipError_t e) {
-        if (fe == hipSuccess)
-            fe = e;
-    };
     // (no d_msg: its size, d_count[1], meets no capacity)
-    const hipError_t e = launch_plan(
-        s, wire, wire_len, fs, n, stream_first, n_streams, state, state, UINT64_MAX, count, 4, info, plans, err,
-        [&](uint32_t nb) {
-            if (plans.assembly == WSG_ASSEMBLY_RFC) {
-                keep(launch_rfc_reply_local(s, false, wire, info, n, plan, plans.rfc, rule, msgs, nullptr));
-                k_reply_blocks<false><<<1, BLOCK, 0, s>>>(plan, nb, n, reply_cap, count, err);
-                keep(launch_rfc_reply_finalize(s, false, info, n, stream_first, n_streams, plan, plans.rfc, rule,
-                                               send_key, msgs, reply, reply_cap, reply_off, stream_reply, pieces,
-                                               pieces_cap, nullptr, nullptr));
-                return;
-            }
-            k_reply_local<false><<<nb, BLOCK, 0, s>>>(wire, info, n, stream_first, state, plan, rule, msgs, nullptr);
-            k_reply_blocks<false><<<1, BLOCK, 0, s>>>(plan, nb, n, reply_cap, count, err);
-            k_reply_finalize<false><<<nb, BLOCK, 0, s>>>(info, n, stream_first, n_streams, plan, rule, send_key, msgs,
-                                                         reply, reply_cap, reply_off, stream_reply, pieces, pieces_cap,
-                                                         nullptr, nullptr);
-        });
+    const hipError_t e = launch_plan(s, b, state, state, UINT64_MAX, o, 4, x, [&](uint32_t nb) {
+        fe = launch_reply_kernels<false>(s, nb, b, state, r, o, x, nullptr);
+    });
     return fe != hipSuccess ? fe : e;
 }
 
-hipError_t launch_reply_checked_plan(hipStream_t s, int stream_grid, const uint8_t* wire, uint64_t wire_len,
-                                     const uint64_t* fs, uint32_t n, const uint32_t* stream_first, uint32_t n_streams,
-                                     wsg_stream_state* state, wsg_proto_state* proto, uint32_t role,
-                                     uint64_t max_message, const wsg_proto_verdict* also, const ReplyRule& rule,
-                                     const uint32_t* send_key, uint8_t* reply, uint64_t reply_cap, uint64_t* reply_off,
-                                     uint64_t* stream_reply, uint64_t* close_off, wsg_proto_verdict* verdict,
-                                     uint64_t* result, wsg_msg* msgs, uint64_t* count, wsg_recv_info* info,
-                                     const MsgPlans& plans, const ProtoPlan& pplan, MsgPiece* pieces,
-                                     uint64_t pieces_cap, unsigned long long* err, const Utf8Inside* utf8)
+hipError_t launch_reply_checked_plan(hipStream_t s, int stream_grid, const Batch& b, wsg_stream_state* state,
+                                     const ProtoOps& p, const ProtoPlan& pplan, const ReplyOut& r, const MsgOut& o,
+                                     const MsgScratch& x, const Utf8Inside* utf8)
 {
-    const MsgPlan& plan = plans.ref;
-    const bool rfc = plans.assembly == WSG_ASSEMBLY_RFC;
     hipError_t pe = hipSuccess;   // of the other sources' launchers (each has taken its launch's error)
     const auto keep = [&pe](hipError_t e) {
         if (pe == hipSuccess)
             pe = e;
     };
-    if (n == 0) {   // no reply, no close frame, nothing judged: the seeds, and d_proto as it came
-        if (hipError_t e = hipMemsetAsync(plan.rtot, 0, 4 * sizeof(uint64_t), s); e != hipSuccess)
+    if (b.n == 0) {   // no reply, no close frame, nothing judged: the seeds, and d_proto as it came
+        if (hipError_t e = reply_of_none(s, b.n_streams, x.plans.ref, r); e != hipSuccess)
             return e;
-        if (hipError_t e = hipMemsetAsync(reply_off, 0, sizeof(uint64_t), s); e != hipSuccess)
-            return e;
-        if (hipError_t e = hipMemsetAsync(stream_reply, 0, (uint64_t(n_streams) + 1) * sizeof(uint64_t), s);
-            e != hipSuccess)
-            return e;
-        if (n_streams)
-            if (hipError_t e = hipMemsetAsync(close_off, 0xFF, uint64_t(n_streams) * sizeof(uint64_t), s);
-                e != hipSuccess)
-                return e;
-        keep(launch_proto_scan(s, info, n, stream_first, n_streams, proto, pplan, verdict, result));
-        keep(launch_proto_finish(s, stream_grid, n, stream_first, n_streams, state, proto, pplan, verdict, result));
+        keep(launch_proto_scan(s, b, o.info, p, pplan));
+        keep(launch_proto_finish(s, stream_grid, b, state, p, pplan));
         if (utf8)   // no record: d_utf8_result's seed is its value
-            keep(launch_utf8_init(s, 1, msgs, count, 0, utf8->valid, utf8->result));
+            keep(launch_utf8_init(s, 1, o.msgs, o.count, 0, utf8->valid, utf8->result));
     }
-    const hipError_t e = launch_plan(
-        s, wire, wire_len, fs, n, stream_first, n_streams, state, state, UINT64_MAX, count, 5, info, plans, err,
-        [&](uint32_t nb) {   // (n > 0, so n_streams > 0: the caller checks)
-            const uint64_t* v = reinterpret_cast<const uint64_t*>(verdict);
-            if (rfc)
-                keep(launch_rfc_state(s, n, stream_first, n_streams, state, plans.rfc, true));
-            else
-                k_msg_consumed<<<(n_streams + BLOCK - 1) / BLOCK, BLOCK, 0, s>>>(n, stream_first, n_streams, state,
-                                                                                  plan);
-            keep(launch_proto_scan(s, info, n, stream_first, n_streams, proto, pplan, verdict, result));
-            keep(launch_proto_judge(s, wire, wire_len, info, n, stream_first, state, proto, role, max_message, pplan,
-                                    verdict));
-            if (utf8) {
-                // wsg_reply_validated: the dense piece records (the reply's replace them below), the
-                // check from the wire over them, its verdicts beside the caller's
-                keep(launch_finalize(s, nb, wire, info, n, stream_first, state, plans, msgs, pieces, pieces_cap));
-                keep(launch_utf8_init(s, utf8->rec_grid, msgs, count, n, utf8->valid, utf8->result));
-                if (utf8->which)
-                    keep(launch_utf8_wire(s, utf8->wire_grid, wire, wire_len, plan, pieces, pieces_cap, msgs, count,
-                                          n, utf8->which, utf8->valid));
-                keep(launch_utf8_count(s, utf8->rec_grid, msgs, count, n, UINT64_MAX, utf8->which, utf8->valid,
-                                       utf8->result));
-                keep(launch_utf8_verdicts_over(s, utf8->rec_grid, stream_grid, n, stream_first, also, msgs, count, n,
-                                               utf8->which, utf8->valid, n_streams, utf8->also));
-                also = reinterpret_cast<const wsg_proto_verdict*>(utf8->also);
-            }
-            if (also)
-                keep(launch_proto_merge(s, stream_grid, n, stream_first, n_streams, also, verdict));
-            keep(launch_proto_finish(s, stream_grid, n, stream_first, n_streams, state, proto, pplan, verdict, result));
-            if (rfc) {
-                keep(launch_rfc_reply_local(s, true, wire, info, n, plan, plans.rfc, rule, msgs, v));
-                k_reply_blocks<true><<<1, BLOCK, 0, s>>>(plan, nb, n, reply_cap, count, err);
-                keep(launch_rfc_reply_finalize(s, true, info, n, stream_first, n_streams, plan, plans.rfc, rule,
-                                               send_key, msgs, reply, reply_cap, reply_off, stream_reply, pieces,
-                                               pieces_cap, v, close_off));
-                return;
-            }
-            k_reply_local<true><<<nb, BLOCK, 0, s>>>(wire, info, n, stream_first, state, plan, rule, msgs, v);
-            k_reply_blocks<true><<<1, BLOCK, 0, s>>>(plan, nb, n, reply_cap, count, err);
-            k_reply_finalize<true><<<nb, BLOCK, 0, s>>>(info, n, stream_first, n_streams, plan, rule, send_key, msgs,
-                                                          reply, reply_cap, reply_off, stream_reply, pieces,
-                                                          pieces_cap, v, close_off);
-        });
+    const hipError_t e = launch_plan(s, b, state, state, UINT64_MAX, o, 5, x, [&](uint32_t nb) {
+        // (n > 0, so n_streams > 0: the caller checks)
+        if (x.plans.assembly == WSG_ASSEMBLY_RFC)
+            keep(launch_rfc_state(s, b.n, b.stream_first, b.n_streams, state, x.plans.rfc, true));
+        else
+            k_msg_consumed<<<(b.n_streams + BLOCK - 1) / BLOCK, BLOCK, 0, s>>>(b.n, b.stream_first, b.n_streams, state,
+                                                                                x.plans.ref);
+        keep(launch_proto_scan(s, b, o.info, p, pplan));
+        keep(launch_proto_judge(s, b, o.info, state, p, pplan));
+        const wsg_proto_verdict* also = p.also;
+        if (utf8) {
+            // wsg_reply_validated: the dense piece records (the reply's replace them below), the
+            // check from the wire over them, its verdicts beside the caller's
+            keep(launch_finalize(s, nb, b, state, o, x));
+            keep(launch_utf8_init(s, utf8->rec_grid, o.msgs, o.count, b.n, utf8->valid, utf8->result));
+            if (utf8->which)
+                keep(launch_utf8_wire(s, utf8->wire_grid, b, o, x, utf8->which, utf8->valid));
+            keep(launch_utf8_count(s, utf8->rec_grid, o.msgs, o.count, b.n, UINT64_MAX, utf8->which, utf8->valid,
+                                   utf8->result));
+            keep(launch_utf8_verdicts_over(s, stream_grid, b, also, o, *utf8));
+            also = reinterpret_cast<const wsg_proto_verdict*>(utf8->also);
+        }
+        if (also)
+            keep(launch_proto_merge(s, stream_grid, b.n, b.stream_first, b.n_streams, also, p.verdict));
+        keep(launch_proto_finish(s, stream_grid, b, state, p, pplan));
+        keep(launch_reply_kernels<true>(s, nb, b, state, r, o, x, reinterpret_cast<const uint64_t*>(p.verdict)));
+    });
     return pe != hipSuccess ? pe : e;
-}
-
-hipError_t launch_reply_gather(hipStream_t s, int grid, const uint8_t* wire, const MsgPlan& plan,
-                               const MsgPiece* pieces, uint64_t pieces_cap, uint8_t* reply, uint64_t reply_cap)
-{
-    k_msg_gather<<<grid, BLOCK, 0, s>>>(wire, plan.rtot, pieces, pieces_cap, reply, reply_cap);
-    return hipGetLastError();
 }
 
 } // namespace wsg

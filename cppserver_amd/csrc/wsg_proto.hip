@@ -247,29 +247,26 @@ uint64_t proto_plan_layout(uint8_t* base, uint32_t n, uint32_t ns, ProtoPlan* pl
     return c.at;
 }
 
-hipError_t launch_proto_scan(hipStream_t s, const wsg_recv_info* info, uint32_t n, const uint32_t* stream_first,
-                             uint32_t n_streams, const wsg_proto_state* proto, const ProtoPlan& plan,
-                             wsg_proto_verdict* verdict, uint64_t* result)
+hipError_t launch_proto_scan(hipStream_t s, const Batch& b, const wsg_recv_info* info, const ProtoOps& p,
+                             const ProtoPlan& plan)
 {
     // with no stream no frame has one: nothing is judged
-    const uint32_t nb = n_streams ? uint32_t((uint64_t(n) + BLOCK - 1) / BLOCK) : 0u;
-    const uint32_t seed_blocks = uint32_t((uint64_t(n_streams) + BLOCK - 1) / BLOCK);
-    k_proto_local<<<max(max(nb, seed_blocks), 1u), BLOCK, 0, s>>>(info, n, stream_first, n_streams, proto, plan, nb,
-                                                                  reinterpret_cast<unsigned long long*>(verdict),
-                                                                  result);
+    const uint32_t nb = b.n_streams ? uint32_t((uint64_t(b.n) + BLOCK - 1) / BLOCK) : 0u;
+    const uint32_t seed_blocks = uint32_t((uint64_t(b.n_streams) + BLOCK - 1) / BLOCK);
+    k_proto_local<<<max(max(nb, seed_blocks), 1u), BLOCK, 0, s>>>(info, b.n, b.stream_first, b.n_streams, p.proto, plan,
+                                                                  nb, reinterpret_cast<unsigned long long*>(p.verdict),
+                                                                  p.result);
     if (nb)
         k_proto_blocks<<<1, BLOCK, 0, s>>>(plan, nb);
     return hipGetLastError();
 }
 
-hipError_t launch_proto_judge(hipStream_t s, const uint8_t* wire, uint64_t wire_len, const wsg_recv_info* info,
-                              uint32_t n, const uint32_t* stream_first, const wsg_stream_state* state,
-                              const wsg_proto_state* proto, uint32_t role, uint64_t max_message, const ProtoPlan& plan,
-                              wsg_proto_verdict* verdict)
+hipError_t launch_proto_judge(hipStream_t s, const Batch& b, const wsg_recv_info* info,
+                              const wsg_stream_state* state, const ProtoOps& p, const ProtoPlan& plan)
 {
-    const uint32_t nb = uint32_t((uint64_t(n) + BLOCK - 1) / BLOCK);
-    k_proto_judge<<<nb, BLOCK, 0, s>>>(wire, wire_len, info, n, stream_first, state, proto, role, max_message, plan,
-                                       reinterpret_cast<unsigned long long*>(verdict));
+    const uint32_t nb = uint32_t((uint64_t(b.n) + BLOCK - 1) / BLOCK);
+    k_proto_judge<<<nb, BLOCK, 0, s>>>(b.wire, b.wire_len, info, b.n, b.stream_first, state, p.proto, p.role,
+                                       p.max_message, plan, reinterpret_cast<unsigned long long*>(p.verdict));
     return hipGetLastError();
 }
 
@@ -281,13 +278,12 @@ hipError_t launch_proto_merge(hipStream_t s, int grid, uint32_t n, const uint32_
     return hipGetLastError();
 }
 
-hipError_t launch_proto_finish(hipStream_t s, int grid, uint32_t n, const uint32_t* stream_first, uint32_t n_streams,
-                               const wsg_stream_state* state, wsg_proto_state* proto, const ProtoPlan& plan,
-                               const wsg_proto_verdict* verdict, uint64_t* result)
+hipError_t launch_proto_finish(hipStream_t s, int grid, const Batch& b, const wsg_stream_state* state,
+                               const ProtoOps& p, const ProtoPlan& plan)
 {
-    k_proto_finish<<<grid, BLOCK, 0, s>>>(n, stream_first, n_streams, state, proto, plan,
-                                          reinterpret_cast<const uint64_t*>(verdict),
-                                          reinterpret_cast<unsigned long long*>(result));
+    k_proto_finish<<<grid, BLOCK, 0, s>>>(b.n, b.stream_first, b.n_streams, state, p.proto, plan,
+                                          reinterpret_cast<const uint64_t*>(p.verdict),
+                                          reinterpret_cast<unsigned long long*>(p.result));
     return hipGetLastError();
 }
 

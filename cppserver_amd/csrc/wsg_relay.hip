@@ -324,19 +324,15 @@ uint64_t relay_plan_layout(uint8_t* base, uint32_t n, uint32_t ns, RelayPlan* pl
     return c.at;
 }
 
-hipError_t launch_relay_plan(hipStream_t s, const wsg_recv_info* info, uint32_t n, uint32_t n_streams,
-                             const wsg_msg* msgs, const wsg_proto_verdict* verdict, const MsgPlans& plans,
-                             const ReplyRule& caller_rule, const uint32_t* order, const uint32_t* group_first,
-                             uint32_t n_groups, uint8_t* relay, uint64_t relay_cap, uint64_t* relay_off,
-                             uint64_t* group_relay, uint64_t* count, const RelayPlan& Q, MsgPiece* pieces,
-                             uint64_t pieces_cap, unsigned long long* err)
+hipError_t launch_relay_plan(hipStream_t s, const Batch& b, const MsgOut& o, const wsg_proto_verdict* verdict,
+                             const RelayArgs& relay, const RelayPlan& Q, const MsgScratch& x)
 {
+    const uint32_t n = b.n, n_streams = b.n_streams;
     const uint32_t nb = uint32_t((uint64_t(n) + BLOCK - 1) / BLOCK);
     const uint32_t nbs = uint32_t((uint64_t(n_streams) + BLOCK - 1) / BLOCK);
     const uint64_t* v = reinterpret_cast<const uint64_t*>(verdict);
-    const uint64_t* ptot = plans.ref.tot;
-    ReplyRule rule = caller_rule;
-    rule.mask = 0;   // a relay frame is unmasked (reply_size reads the rule's mask)
+    const uint64_t* ptot = x.plans.ref.tot;
+    const ReplyRule rule = reply_rule(relay.relay_op, 0);   // a relay frame is unmasked (reply_size reads the mask)
     if (n_streams) {
         const uint64_t run = reinterpret_cast<uint8_t*>(Q.inv) - reinterpret_cast<uint8_t*>(Q.mfirst);
         if (hipError_t e = hipMemsetAsync(Q.mfirst, 0, run, s); e != hipSuccess)
@@ -346,28 +342,22 @@ hipError_t launch_relay_plan(hipStream_t s, const wsg_recv_info* info, uint32_t 
     }
     if (hipError_t e = hipMemsetAsync(Q.bad, 0xFF, sizeof(uint64_t), s); e != hipSuccess)
         return e;
-    k_relay_local<<<(nb ? nb : 1u), BLOCK, 0, s>>>(msgs, ptot, n_streams, v, rule, order, Q);
+    k_relay_local<<<(nb ? nb : 1u), BLOCK, 0, s>>>(o.msgs, ptot, n_streams, v, rule, relay.order, Q);
     if (n) {
-        if (plans.assembly == WSG_ASSEMBLY_RFC)
-            k_relay_frames<true><<<nb, BLOCK, 0, s>>>(info, n, msgs, ptot, n_streams, v, rule, plans.rfc.eo, Q);
+        if (x.plans.assembly == WSG_ASSEMBLY_RFC)
+            k_relay_frames<true><<<nb, BLOCK, 0, s>>>(o.info, n, o.msgs, ptot, n_streams, v, rule, x.plans.rfc.eo, Q);
         else
-            k_relay_frames<false><<<nb, BLOCK, 0, s>>>(info, n, msgs, ptot, n_streams, v, rule, nullptr, Q);
+            k_relay_frames<false><<<nb, BLOCK, 0, s>>>(o.info, n, o.msgs, ptot, n_streams, v, rule, nullptr, Q);
     }
     k_relay_blocks<<<4, BLOCK, 0, s>>>(Q, nb);
-    k_relay_streams_local<<<(nbs ? nbs : 1u), BLOCK, 0, s>>>(ptot, n_streams, order, group_first, n_groups, Q);
-    k_relay_streams_blocks<<<1, BLOCK, 0, s>>>(Q, nbs, n, relay_cap, count, err);
-    k_relay_finalize<<<(nb ? nb : 1u), BLOCK, 0, s>>>(info, n, msgs, ptot, n_streams, v, rule, order, group_first,
-                                                         n_groups, Q, relay, relay_cap, relay_off, group_relay, pieces,
-                                                         pieces_cap);
+    k_relay_streams_local<<<(nbs ? nbs : 1u), BLOCK, 0, s>>>(ptot, n_streams, relay.order, relay.group_first,
+                                                              relay.n_groups, Q);
+    k_relay_streams_blocks<<<1, BLOCK, 0, s>>>(Q, nbs, n, relay.relay_cap, o.count, x.err);
+    k_relay_finalize<<<(nb ? nb : 1u), BLOCK, 0, s>>>(o.info, n, o.msgs, ptot, n_streams, v, rule, relay.order,
+                                                         relay.group_first, relay.n_groups, Q, relay.relay,
+                                                         relay.relay_cap, relay.relay_off, relay.group_relay, x.pieces,
+                                                         x.pieces_cap);
     return hipGetLastError();
-}
-
-hipError_t launch_relay_gather(hipStream_t s, int grid, const uint8_t* wire, const RelayPlan& Q,
-                               const MsgPiece* pieces, uint64_t pieces_cap, uint8_t* relay, uint64_t relay_cap)
-{
-    MsgPlan as_reply{};
-    as_reply.rtot = Q.gtot;
-    return launch_reply_gather(s, grid, wire, as_reply, pieces, pieces_cap, relay, relay_cap);
 }
 
 } // namespace wsg

@@ -518,25 +518,22 @@ __global__ __launch_bounds__(BLOCK) void k_utf8_also_seed(uint32_t n, const uint
     }
 }
 
-hipError_t launch_utf8_verdicts_over(hipStream_t s, int rec_grid, int stream_grid, uint32_t n,
-                                     const uint32_t* stream_first, const wsg_proto_verdict* also_in,
-                                     const wsg_msg* msgs, const uint64_t* count, uint32_t msg_room, uint32_t which,
-                                     const uint64_t* valid, uint32_t n_streams, uint64_t* also)
+hipError_t launch_utf8_verdicts_over(hipStream_t s, int stream_grid, const Batch& b,
+                                     const wsg_proto_verdict* also_in, const MsgOut& o, const Utf8Inside& u)
 {
-    unsigned long long* a = reinterpret_cast<unsigned long long*>(also);
-    k_utf8_also_seed<<<stream_grid, BLOCK, 0, s>>>(n, stream_first, n_streams,
+    unsigned long long* a = reinterpret_cast<unsigned long long*>(u.also);
+    k_utf8_also_seed<<<stream_grid, BLOCK, 0, s>>>(b.n, b.stream_first, b.n_streams,
                                                    reinterpret_cast<const uint64_t*>(also_in), a);
-    if (msg_room && n_streams && which)
-        k_utf8_verdicts<<<rec_grid, BLOCK, 0, s>>>(msgs, count, msg_room, which, valid, n_streams, a);
+    if (b.n && b.n_streams && u.which)
+        k_utf8_verdicts<<<u.rec_grid, BLOCK, 0, s>>>(o.msgs, o.count, b.n, u.which, u.valid, b.n_streams, a);
     return hipGetLastError();
 }
 
-hipError_t launch_utf8_wire(hipStream_t s, int grid, const uint8_t* wire, uint64_t wire_len, const MsgPlan& plan,
-                            const MsgPiece* pieces, uint64_t pieces_cap, const wsg_msg* msgs, const uint64_t* count,
-                            uint32_t msg_room, uint32_t which, uint64_t* valid)
+hipError_t launch_utf8_wire(hipStream_t s, int grid, const Batch& b, const MsgOut& o, const MsgScratch& x,
+                            uint32_t which, uint64_t* valid)
 {
-    k_utf8_wire<<<grid, BLOCK, 0, s>>>(wire, wire_len, plan.tot, pieces, pieces_cap, msgs, count, msg_room, which,
-                                       reinterpret_cast<unsigned long long*>(valid));
+    k_utf8_wire<<<grid, BLOCK, 0, s>>>(b.wire, b.wire_len, x.plans.ref.tot, x.pieces, x.pieces_cap, o.msgs, o.count,
+                                       b.n, which, reinterpret_cast<unsigned long long*>(valid));
     return hipGetLastError();
 }
 

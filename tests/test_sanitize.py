@@ -56,6 +56,16 @@ def test_sanitized_lane_plan():
     _run(os.path.join(CPP, "_build", "san", "test_lane_plan"))
 
 
+def test_sanitized_capi_args():
+    """The argument checks of the device entry points (cppserver_amd/csrc/wsg_args.h:
+    one table of operand rows per family) without a device: for every entry
+    point, what it accepts and refuses (null, misaligned, no frame and no
+    stream) and, under WSG_CHECK, the operands and bytes it looks up, against
+    rows written out from the contract (tests/cpp/test_capi_args.cpp)."""
+    _make("sanitize")
+    _run(os.path.join(CPP, "_build", "san", "test_capi_args"))
+
+
 def test_batch_threads_tsan():
     """Forget / destroy a connection or transport on one thread
     while another flushes, and destroy a session whose frames sit in another

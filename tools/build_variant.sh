@@ -23,7 +23,7 @@ for k in ${KSRC:-$csrc/wsg_decode.hip $csrc/wsg_encode.hip $csrc/wsg_fanout.hip 
     kobjs="$kobjs $o"
 done
 pobjs=
-for p in ${PSRC-$csrc/wsg_messages.hip $csrc/wsg_frames.hip $csrc/wsg_utf8.hip $csrc/wsg_proto.hip $csrc/wsg_assembly.hip $csrc/wsg_upgrade.hip}; do
+for p in ${PSRC-$csrc/wsg_messages.hip $csrc/wsg_frames.hip $csrc/wsg_utf8.hip $csrc/wsg_proto.hip $csrc/wsg_assembly.hip $csrc/wsg_upgrade.hip $csrc/wsg_carry.hip $csrc/wsg_relay.hip}; do
     o=p_$(basename "$p" .hip).o
     $H $F -I$csrc -c "$p" -o "$o"
     pobjs="$pobjs $o"
