@@ -25,6 +25,8 @@ from .layout import (  # noqa: F401  (re-exported)
     UP_ACCEPTED, UP_BAD_CONNECTION, UP_BAD_HTTP, UP_BAD_UPGRADE, UP_BAD_VERSION, UP_EMPTY_KEY, UP_INCOMPLETE,
     UP_MISSING, UP_NOT_GET, UP_NOT_WEBSOCKET, UP_TOO_LONG, UPGRADE_DTYPE, UPGRADE_RESP_MAX, upgrade_plan,
     STREAM_READ, carry_plan,
+    UC_ACCEPTED, UC_BAD_ACCEPT, UC_BAD_CONNECTION, UC_BAD_HTTP, UC_BAD_UPGRADE, UC_INCOMPLETE, UC_MISSING, UC_NOT_101,
+    UC_TOO_LONG, UPGRADE_REPLY_DTYPE, upgrade_client_plan,
     CHAT_RELAY, CHAT_REPLY, relay_plan, relay_tables_bad,
 )
 
@@ -101,6 +103,10 @@ def lib(path=None):
         "wsg_upgrade_streams": (ci, [vp, vp, u64, vp, u32, u64, vp, vp, u64, vp, vp, vp]),
         "wsg_carry_streams": (ci, [vp, vp, u64, vp, u32, vp, vp, u64, vp, vp, u64, vp, vp, vp]),
         "wsg_upgrade_judge": (ci, [vp, u64, u64, vp, vp, u32, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "wsg_upgrade_client_streams": (ci, [vp, vp, u64, vp, u32, vp, u64, vp, vp, vp]),
+        "wsg_upgrade_requests": (ci, [vp, vp, u32, u32, vp, u32, vp, u64, vp]),
+        "wsg_upgrade_client_judge": (ci, [vp, u64, vp, u64, vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "wsg_upgrade_request": (ci, [vp, u32, u32, vp, vp]),
         "wsg_encode_batch": (ci, [vp, vp, vp, u32, vp, u64, vp, vp]),
         "wsg_fanout_encode": (ci, [vp, vp, u64, vp, u32, ctypes.c_uint8, ci, vp, u64, vp]),
         "wsg_fanout_encode_many": (ci, [vp, vp, vp, vp, vp, u32, vp, u32, ci, vp, u64, vp, vp]),
@@ -237,6 +243,32 @@ def upgrade_judge(data, max_request=0, resp_cap=UPGRADE_RESP_MAX):
         raise WSGError(rc, "wsg_upgrade_judge")
     sent = resp[: int(rec["resp_len"][0])].tobytes() if rc == WSG_OK else b""
     return rc, rec[0].copy(), sent, int(consumed.value), int(need.value)
+
+
+def upgrade_client_judge(data, nonce, max_response=0):
+    """wsg_upgrade_client_judge: one client connection's first bytes judged on
+    the host, against the 16-byte ``nonce``, by the rule the kernels run.
+    Returns (record, consumed, need): one UPGRADE_REPLY_DTYPE record and the
+    span's outputs."""
+    data, nonce = bytes(data), bytes(nonce)
+    if len(nonce) != 16:
+        raise WSGError(WSG_EINVAL, "upgrade_client_judge: the nonce has 16 bytes")
+    rec = np.zeros(1, dtype=UPGRADE_REPLY_DTYPE)
+    consumed, need = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    _check(lib().wsg_upgrade_client_judge(data, len(data), nonce, int(max_response), _np_ptr(rec),
+                                          ctypes.byref(consumed), ctypes.byref(need)), "wsg_upgrade_client_judge")
+    return rec[0].copy(), int(consumed.value), int(need.value)
+
+
+def upgrade_request(tpl, key_at, nonce):
+    """wsg_upgrade_request: the request template with Base64(nonce) in its
+    24-byte hole at ``key_at``."""
+    tpl, nonce = bytes(tpl), bytes(nonce)
+    if len(nonce) != 16:
+        raise WSGError(WSG_EINVAL, "upgrade_request: the nonce has 16 bytes")
+    out = ctypes.create_string_buffer(max(len(tpl), 1))
+    _check(lib().wsg_upgrade_request(tpl, len(tpl), int(key_at), nonce, out), "wsg_upgrade_request")
+    return out.raw[: len(tpl)]
 
 
 class _Pinned:
@@ -579,6 +611,57 @@ class Codec:
                                          self._stream(stream))
         _check(rc, "wsg_upgrade_streams")
         return up, resp, resp_off, count
+
+    def upgrade_client_streams(self, wire, spans, nonces, max_response=0, stream=None, up=None, count=None):
+        """wsg_upgrade_client_streams: the upgrade response at the head of
+        every stream of ``spans`` (consumed and need out, in place) judged on
+        the device against ``nonces`` (uint8, 16 bytes a stream).  Returns
+        (up, count): uint8[n_streams * 32] UPGRADE_REPLY_DTYPE records and
+        count int64[3] = [accepted, whole but not accepted, incomplete]."""
+        t = self._torch
+        ns = int(spans.numel()) // STREAM_SPAN.itemsize
+        if spans.element_size() != 1 or int(spans.numel()) != ns * STREAM_SPAN.itemsize:
+            raise WSGError(WSG_EINVAL, "upgrade_client_streams: spans must be uint8, n_streams * 32 bytes")
+        if nonces.element_size() != 1 or int(nonces.numel()) < 16 * ns:
+            raise WSGError(WSG_EINVAL, "upgrade_client_streams: nonces must be uint8, 16 bytes a stream")
+        dev = wire.device
+        if up is None:
+            up = t.empty(max(ns, 1) * UPGRADE_REPLY_DTYPE.itemsize, dtype=t.uint8, device=dev)
+        if count is None:
+            count = t.empty(3, dtype=t.int64, device=dev)
+        if (int(up.numel()) * up.element_size() < ns * UPGRADE_REPLY_DTYPE.itemsize or count.element_size() != 8
+                or int(count.numel()) < 3):
+            raise WSGError(WSG_EINVAL, "upgrade_client_streams: a buffer is smaller than the batch needs")
+        rc = self._L.wsg_upgrade_client_streams(self._ctx, ctypes.c_void_p(wire.data_ptr()), wire.numel(),
+                                                ctypes.c_void_p(spans.data_ptr()), ns,
+                                                ctypes.c_void_p(nonces.data_ptr()), int(max_response),
+                                                ctypes.c_void_p(up.data_ptr()), ctypes.c_void_p(count.data_ptr()),
+                                                self._stream(stream))
+        _check(rc, "wsg_upgrade_client_streams")
+        return up, count
+
+    def upgrade_requests(self, tpl, key_at, nonces, req=None, req_cap=None, stream=None):
+        """wsg_upgrade_requests: one request per 16 bytes of ``nonces``
+        (uint8), each the template ``tpl`` (uint8, a 24-byte hole at
+        ``key_at``) with Base64 of its nonce in the hole.  Returns the
+        requests back to back (``req_cap`` bytes of room; default exactly
+        what they need)."""
+        t = self._torch
+        n = int(nonces.numel()) // 16
+        tpl_len = int(tpl.numel())
+        if tpl.element_size() != 1 or nonces.element_size() != 1 or int(nonces.numel()) != 16 * n:
+            raise WSGError(WSG_EINVAL, "upgrade_requests: tpl and nonces must be uint8, 16 bytes a nonce")
+        if req_cap is None:
+            req_cap = n * tpl_len if req is None else int(req.numel())
+        if req is None:
+            req = t.empty(max(int(req_cap), 1), dtype=t.uint8, device=tpl.device)
+        if req.element_size() != 1 or int(req_cap) > int(req.numel()):
+            raise WSGError(WSG_EINVAL, "upgrade_requests: req is smaller than req_cap")
+        rc = self._L.wsg_upgrade_requests(self._ctx, ctypes.c_void_p(tpl.data_ptr()), tpl_len, int(key_at),
+                                          ctypes.c_void_p(nonces.data_ptr()), n, ctypes.c_void_p(req.data_ptr()),
+                                          int(req_cap), self._stream(stream))
+        _check(rc, "wsg_upgrade_requests")
+        return req
 
     def carry_streams(self, wire, spans, new, reads, close_off=None, next=None, next_cap=None, next_spans=None,
                       count=None, stream=None):

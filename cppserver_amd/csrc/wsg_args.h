@@ -179,6 +179,30 @@ inline int args_upgrade_streams(const void* d_wire, uint64_t wire_len, const voi
                       check);
 }
 
+inline int args_upgrade_client(const void* d_wire, uint64_t wire_len, const void* span, uint32_t n_streams,
+                               const void* nonce, const void* up, const void* count, bool check)
+{
+    if (n_streams == UINT32_MAX)
+        return WSG_EINVAL;
+    const uint64_t ns = n_streams;
+    return args_check({wire(d_wire, wire_len), sized(span, ns * sizeof(wsg_stream_span), 8), sized(nonce, ns * 16, 16),
+                       sized(up, ns * sizeof(wsg_upgrade_reply), 8), always(count, 3 * 8, 8)},
+                      check);
+}
+
+// wsg_upgrade_requests; total = n * tpl_len, which the entry point has held
+// against req_cap (WSG_ENOMEM) when it asks.  The template is read in 16-byte
+// blocks; nothing is needed for no request.
+inline int args_upgrade_requests(const void* tpl, uint32_t tpl_len, uint32_t key_at, const void* nonce, uint32_t n,
+                                 const void* req, uint64_t total, bool check)
+{
+    if (uint64_t(key_at) + 24 > tpl_len)
+        return WSG_EINVAL;
+    return args_check({when(n != 0, tpl, (uint64_t(tpl_len) + 15) & ~uint64_t(15), 16),
+                       sized(nonce, uint64_t(n) * 16, 16), when(n != 0, req, total, 16)},
+                      check && n != 0);
+}
+
 // wsg_carry_streams: the next wire overlaps neither source, the next spans are
 // not the spans.
 inline int args_carry_streams(const uint8_t* d_wire, uint64_t wire_len, const void* span, uint32_t n_streams,

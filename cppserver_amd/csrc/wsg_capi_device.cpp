@@ -293,6 +293,54 @@ int wsg_upgrade_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, ws
     return scratch_leave(c->frame_order, s, ordered);
 }
 
+// The client's half of the handshake: the streams' expected digests, one wave
+// per stream judges the response, the counts.  The framer's scratch and its
+// order, as wsg_upgrade_streams.
+int wsg_upgrade_client_streams(wsg_ctx* c, const uint8_t* d_wire, uint64_t wire_len, wsg_stream_span* d_span,
+                               uint32_t n_streams, const uint8_t* d_nonce, uint64_t max_response,
+                               wsg_upgrade_reply* d_up, uint64_t* d_count, void* stream)
+{
+    if (!c || wsg::args_upgrade_client(d_wire, wire_len, d_span, n_streams, d_nonce, d_up, d_count, c->check))
+        return WSG_EINVAL;
+    hipStream_t s = as_stream(stream);
+    if (int rc = ensure_array(c->d_frame_plan, c->frame_plan_cap, wsg::upclient_plan_layout(nullptr, n_streams, nullptr)))
+        return rc;
+    wsg::UpClientPlan plan;
+    wsg::upclient_plan_layout(c->d_frame_plan, n_streams, &plan);
+    bool ordered = false;
+    if (int rc = scratch_enter(c->frame_order, s, &ordered))
+        return rc;
+    const int t = n_streams ? timing_begin(c, s) : -1;
+    WSG_HIP(wsg::launch_upgrade_client_streams(s, grid_for(c, ceil_div(n_streams, wsg::BLOCK / 64), c->dec_blocks_per_cu),
+                                               d_wire, wire_len, d_span, n_streams, d_nonce, max_response, d_up,
+                                               d_count, plan, c->d_err));
+    timing_end(c, s, t);
+    return scratch_leave(c->frame_order, s, ordered);
+}
+
+// The requests of those nonces: one kernel, a 16-byte block of d_req per lane.
+// Twice through the arguments, as the fan-out: the capacity has its turn
+// before the allocations are looked up.
+int wsg_upgrade_requests(wsg_ctx* c, const uint8_t* d_tpl, uint32_t tpl_len, uint32_t key_at, const uint8_t* d_nonce,
+                         uint32_t n, uint8_t* d_req, uint64_t req_cap, void* stream)
+{
+    const uint64_t total = uint64_t(n) * tpl_len;
+    if (!c || wsg::args_upgrade_requests(d_tpl, tpl_len, key_at, d_nonce, n, d_req, total, false))
+        return WSG_EINVAL;
+    if (total > req_cap)
+        return WSG_ENOMEM;
+    if (wsg::args_upgrade_requests(d_tpl, tpl_len, key_at, d_nonce, n, d_req, total, c->check))
+        return WSG_EINVAL;
+    if (n == 0)
+        return WSG_OK;
+    hipStream_t s = as_stream(stream);
+    const int t = timing_begin(c, s);
+    WSG_HIP(wsg::launch_upgrade_requests(s, grid_for(c, ceil_div(ceil_div(total, uint64_t(wsg::CHUNK)), wsg::BLOCK)),
+                                         d_tpl, tpl_len, key_at, d_nonce, d_req, total));
+    timing_end(c, s, t);
+    return WSG_OK;
+}
+
 // The carry: per-stream sizes and a scan (one lane per stream), then the copy,
 // which writes every 16-byte chunk of the next wire once.  The framer's
 // scratch and its order: a round is one call or the other at a time.

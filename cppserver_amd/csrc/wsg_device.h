@@ -1,6 +1,6 @@
 // wsg_device.h — device helpers shared by the kernel sources (wsg_decode.hip,
 // wsg_encode.hip, wsg_fanout.hip, wsg_lane_device.hip, wsg_misc.hip,
-// wsg_messages.hip, wsg_frames.hip, wsg_utf8.hip, wsg_proto.hip, wsg_assembly.hip, wsg_upgrade.hip, wsg_carry.hip, wsg_relay.hip): 16-byte loads
+// wsg_messages.hip, wsg_frames.hip, wsg_utf8.hip, wsg_proto.hip, wsg_assembly.hip, wsg_upgrade.hip, wsg_upgrade_client.hip, wsg_carry.hip, wsg_relay.hip): 16-byte loads
 // and stores, byte funnels and shifts, the output tile, the frame parse, the block scan, the wave
 // reductions, the stream search, a _streams call's span, the error latch and the wsg_msg record codec.  Internal linkage: every source gets its own copy.
 #pragma once
@@ -150,6 +150,17 @@ __device__ __forceinline__ uint64_t uni(uint64_t x)
 {
     return uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(uint32_t(x)))) |
            (uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(uint32_t(x >> 32)))) << 32);
+}
+
+// Bytes [0, n) of an 8-byte word as a mask.
+__device__ __forceinline__ uint64_t bytes_below(int64_t n)
+{
+    return n <= 0 ? 0ull : n >= 8 ? ~0ull : (1ull << (8 * n)) - 1ull;
+}
+
+__device__ __forceinline__ uint32_t lane_bcast32(uint32_t v, uint32_t src)
+{
+    return uint32_t(__builtin_amdgcn_readlane(v, int(uni(src))));
 }
 
 // One stream of a _streams call (wave-uniform).

@@ -1,7 +1,7 @@
 // wsg_internal.h — kernel geometry and kernel declarations shared by the
 // kernel sources (wsg_decode.hip, wsg_encode.hip, wsg_fanout.hip,
 // wsg_lane_device.hip, wsg_misc.hip, wsg_messages.hip, wsg_frames.hip,
-// wsg_utf8.hip, wsg_proto.hip, wsg_assembly.hip, wsg_upgrade.hip, wsg_carry.hip, wsg_relay.hip) and the C-ABI implementation (wsg_ctx.h).
+// wsg_utf8.hip, wsg_proto.hip, wsg_assembly.hip, wsg_upgrade.hip, wsg_upgrade_client.hip, wsg_carry.hip, wsg_relay.hip) and the C-ABI implementation (wsg_ctx.h).
 // The launchers take the operand groups of wsg_operands.h by const reference
 // and unpack them at the <<<>>> call: no kernel sees a group.
 #pragma once
@@ -317,6 +317,26 @@ hipError_t launch_upgrade_streams(hipStream_t s, int grid, const uint8_t* wire, 
                                   wsg_stream_span* span, uint32_t ns, uint64_t max_request, wsg_upgrade* up,
                                   uint8_t* resp, uint64_t resp_cap, uint64_t* resp_off, uint64_t* count,
                                   const UpgradePlan& plan, unsigned long long* err);
+
+// ---- the client's upgrade (wsg_upgrade_client_streams; wsg_upgrade_client.hip) ----
+// Scratch of one call, carved out of the framer's device array (one block =
+// BLOCK streams).
+struct UpClientPlan {
+    uint32_t* digest;   // 8 * ns: each stream's 20 expected digest bytes, in memory order, and 12 of zero
+    uint64_t* bsum;     // 3 * nb: block sums of accepted, whole but not accepted, incomplete streams
+};
+uint64_t upclient_plan_layout(uint64_t* base, uint32_t ns, UpClientPlan* plan);
+// Digests (one lane per stream), parse (one wave per stream, grid-stride over
+// `grid` blocks), counts: d_up, the spans' consumed / need, count (3); latches
+// span errors.
+hipError_t launch_upgrade_client_streams(hipStream_t s, int grid, const uint8_t* wire, uint64_t wire_len,
+                                         wsg_stream_span* span, uint32_t ns, const uint8_t* nonce,
+                                         uint64_t max_response, wsg_upgrade_reply* up, uint64_t* count,
+                                         const UpClientPlan& plan, unsigned long long* err);
+// k_upgrade_requests (total = n * tpl_len > 0): every byte of req below total,
+// a 16-byte block per lane, grid-stride over `grid` blocks.
+hipError_t launch_upgrade_requests(hipStream_t s, int grid, const uint8_t* tpl, uint32_t tpl_len, uint32_t key_at,
+                                   const uint8_t* nonce, uint8_t* req, uint64_t total);
 
 // ---- the carry between two rounds (wsg_carry_streams; wsg_carry.hip) --------
 // Scratch of one call, carved out of the framer's device array (one block =

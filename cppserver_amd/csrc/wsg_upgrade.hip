@@ -52,17 +52,6 @@ static_assert(sizeof(wsg_upgrade) == 32 && offsetof(wsg_upgrade, key_len) == 16 
                   offsetof(wsg_upgrade, status) == 28 && offsetof(wsg_upgrade, code) == 30,
               "wsg_upgrade layout (up_record)");
 
-// Bytes [0, n) of an 8-byte word as a mask.
-__device__ __forceinline__ uint64_t bytes_below(int64_t n)
-{
-    return n <= 0 ? 0ull : n >= 8 ? ~0ull : (1ull << (8 * n)) - 1ull;
-}
-
-__device__ __forceinline__ uint32_t lane_bcast32(uint32_t v, uint32_t src)
-{
-    return uint32_t(__builtin_amdgcn_readlane(v, int(uni(src))));
-}
-
 // The request at wire[off, off + len): every argument and the result are
 // wave-uniform.
 __device__ __forceinline__ UpOutcome upgrade_walk(const uint8_t* __restrict__ wire, uint64_t off, uint64_t len,

@@ -916,6 +916,166 @@ def upgrade_plan(wire, spans, max_request=0):
     return up, consumed, need, resp_off, np.frombuffer(b"".join(resp), dtype=np.uint8), count, bad
 
 
+# ---- the client's half of the handshake (wsg_upgrade_client_streams) ---------
+UPGRADE_REPLY_DTYPE = np.dtype([("accept_off", "<u8"), ("body_off", "<u8"), ("accept_len", "<u4"), ("body_len", "<u4"),
+                                ("_zero", "<u4"), ("status", "<u2"), ("code", "u1"), ("_pad", "u1")])
+(UC_INCOMPLETE, UC_ACCEPTED, UC_BAD_HTTP, UC_BAD_CONNECTION, UC_BAD_UPGRADE, UC_BAD_ACCEPT, UC_MISSING, UC_NOT_101,
+ UC_TOO_LONG) = range(9)
+_B64 = b"ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/"
+
+assert UPGRADE_REPLY_DTYPE.itemsize == 32
+
+
+def upgrade_expect(nonce):
+    """SHA-1(Base64(nonce) || GUID): the 20 bytes a client holds the decoded
+    Sec-WebSocket-Accept value against."""
+    import base64
+    import hashlib
+
+    nonce = bytes(nonce)
+    assert len(nonce) == 16
+    return hashlib.sha1(base64.b64encode(nonce) + WS_GUID).digest()
+
+
+def upgrade_request(tpl, key_at, nonce):
+    """wsg_upgrade_request: the template with Base64(nonce) in its 24-byte
+    hole at ``key_at``."""
+    import base64
+
+    tpl, nonce = bytes(tpl), bytes(nonce)
+    assert len(nonce) == 16 and 0 <= key_at and key_at + 24 <= len(tpl)
+    return tpl[:key_at] + base64.b64encode(nonce) + tpl[key_at + 24:]
+
+
+def _accept_ok(value, expect):
+    """The value decoded as WS::Base64Decode does (a byte outside the
+    alphabet is skipped, six bits a letter, a byte whenever eight are held),
+    then strncmp(got, expect, min(len(got), 20))."""
+    got, acc, bits = bytearray(), 0, 0
+    for c in value:
+        v = _B64.find(bytes([c]))
+        if v < 0:
+            continue
+        acc = (acc << 6) | v
+        bits += 6
+        if bits >= 8:
+            bits -= 8
+            got.append((acc >> bits) & 0xFF)
+    for i in range(min(len(got), 20)):
+        if got[i] != expect[i]:
+            return False
+        if got[i] == 0:
+            return True
+    return True
+
+
+def upgrade_client_judge(data, nonce, max_response=0):
+    """One client connection's first bytes as WSClient::onReceived,
+    HTTPResponse::Parse and WebSocket::PerformClientUpgrade judge them against
+    the 16-byte ``nonce``.  Returns a dict: code, status, consumed, need,
+    accept (offset, length) or None, body (offset, length) or None, and fail:
+    the code of the header that ended the walk (0: none), which the classes
+    report through onWSError even where the outcome is UC_ACCEPTED."""
+    data = bytes(data)
+    out = dict(code=UC_TOO_LONG if max_response and len(data) >= max_response else UC_INCOMPLETE, status=0, consumed=0,
+               need=0, accept=None, body=None, fail=0)
+    p = data.find(b"\r\n\r\n")
+    if p < 0:
+        return out
+    hend = p + 4
+    eol = data.find(b"\r\n")
+    line = data[:eol]
+    s1 = line.find(b" ")
+    s2 = line.find(b" ", s1 + 1) if s1 >= 0 else -1
+    digits = line[s1 + 1:s2 if s2 >= 0 else len(line)]
+    bad = s1 <= 0 or len(digits) != 3 or not all(48 <= c <= 57 for c in digits)
+    headers, clen, at = [], 0, eol + 2
+    block_end = max(hend - 2, at)
+    while not bad and at < block_end:
+        e = data.find(b"\r\n", at, block_end)
+        e = block_end if e < 0 else e
+        ln = data[at:e]
+        if ln:
+            colon = ln.find(b":")
+            if colon <= 0:
+                bad = True
+                break
+            k, v = ln[:colon].strip(b" \t"), ln[colon + 1:].strip(b" \t")
+            v_at = at + colon + 1 + (len(ln[colon + 1:]) - len(ln[colon + 1:].lstrip(b" \t")))
+            headers.append((_lower(k), v, v_at))
+            if _lower(k) == b"content-length":
+                clen = 0
+                for c in v:
+                    if not 48 <= c <= 57:
+                        bad = True
+                        break
+                    clen = (clen * 10 + c - 48) % 2**64
+        at = e + 2
+    if bad:
+        out.update(code=UC_BAD_HTTP, consumed=hend)
+        return out
+    if len(data) - hend < clen:
+        out["need"] = min(hend + clen, U64_MAX)
+        return out
+    status = int(digits)
+    out.update(code=UC_NOT_101, status=status, consumed=hend + clen, body=(hend, min(clen, 0xFFFFFFFF)))
+    if status != 101:
+        return out
+    expect = upgrade_expect(nonce)
+    seen, fail = set(), 0
+    for k, v, v_at in headers:
+        if k == b"connection":
+            if _lower(v) != b"upgrade":
+                fail = UC_BAD_CONNECTION
+        elif k == b"upgrade":
+            if _lower(v) != b"websocket":
+                fail = UC_BAD_UPGRADE
+        elif k == b"sec-websocket-accept":
+            out["accept"] = (v_at, min(len(v), 0xFFFFFFFF))
+            if not _accept_ok(v, expect):
+                fail = UC_BAD_ACCEPT
+        else:
+            continue
+        if fail:
+            break
+        seen.add(k)
+    out.update(code=UC_ACCEPTED if len(seen) == 3 else fail or UC_MISSING, fail=fail)
+    return out
+
+
+def upgrade_client_plan(wire, spans, nonces, max_response=0):
+    """wsg_upgrade_client_streams restated on the host: one response per
+    stream ``wire[off, off + len)`` against ``nonces[16 j, 16 j + 16)``.
+    Returns (up, consumed, need, count, bad): UPGRADE_REPLY_DTYPE records, the
+    spans' outputs, count = [accepted, whole but not accepted, incomplete] and
+    the spans latched as WSG_EINVAL (bad_spans)."""
+    wire = np.asarray(wire, dtype=np.uint8)
+    spans = np.asarray(spans, dtype=STREAM_SPAN)
+    nonces = np.asarray(nonces, dtype=np.uint8).reshape(-1)
+    ns = len(spans)
+    assert len(nonces) == 16 * ns
+    bad = bad_spans(len(wire), spans)
+    up = np.zeros(ns, dtype=UPGRADE_REPLY_DTYPE)
+    consumed = np.zeros(ns, dtype=np.uint64)
+    need = np.zeros(ns, dtype=np.uint64)
+    for j in range(ns):
+        if bad[j]:
+            continue
+        off, length = int(spans["off"][j]), int(spans["len"][j])
+        o = upgrade_client_judge(wire[off:off + length].tobytes(), nonces[16 * j:16 * j + 16].tobytes(), max_response)
+        u = up[j]
+        u["code"], u["status"] = o["code"], o["status"]
+        if o["accept"] is not None:
+            u["accept_off"], u["accept_len"] = off + o["accept"][0], o["accept"][1]
+        if o["body"] is not None:
+            u["body_off"], u["body_len"] = off + o["body"][0], o["body"][1]
+        consumed[j], need[j] = o["consumed"], o["need"]
+    code = up["code"]
+    count = np.array([np.sum(code == UC_ACCEPTED), np.sum((code >= UC_BAD_HTTP) & (code <= UC_NOT_101)),
+                      np.sum(code == UC_INCOMPLETE)], dtype=np.uint64)
+    return up, consumed, need, count, bad
+
+
 # wsg_stream_read: where a stream's new bytes lie in a wsg_carry_streams call's d_new.
 STREAM_READ = np.dtype([("off", "<u8"), ("len", "<u8")])
 

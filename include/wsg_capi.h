@@ -696,6 +696,107 @@ int wsg_upgrade_streams(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
 int wsg_upgrade_judge(const uint8_t* buf, uint64_t len, uint64_t max_request, wsg_upgrade* out,
                       uint8_t* resp, uint32_t resp_cap, uint64_t* consumed, uint64_t* need);
 
+/* ---- the client's half of the upgrade handshake on the device -------------- */
+/* (Added without an ABI bump: symbols, a struct and constants only.)
+ *
+ * A client connection's first bytes are the server's answer to its upgrade
+ * request.  wsg_upgrade_client_streams judges one response per stream exactly
+ * as WSClient::onReceived, HTTPResponse::Parse and
+ * WebSocket::PerformClientUpgrade do (csrc/wsg_upgrade_client.h restates them;
+ * DESIGN §26), against the 16-byte nonce the client sent as its key.
+ * The rule.  The header block ends behind the first "\r\n\r\n" (hend); without
+ * one the response is incomplete.  The status line runs to the first "\r\n".
+ * With s1 its first space and s2 the next space behind s1 (or the line's
+ * end), it is well-formed only when s1 exists, s1 > 0 and (s1, s2) is exactly
+ * three ASCII digits, the status; a reason phrase may be missing.  The header
+ * lines are split, trimmed and checked as wsg_upgrade_streams' are, and
+ * Content-Length (without case, the last one wins, a non-digit is malformed,
+ * mod 2^64) gives clen.  Malformed: WSG_UC_BAD_HTTP, consumed = hend, decided
+ * before the body's completeness.  Fewer than clen bytes behind hend:
+ * incomplete.  Else consumed = hend + clen, and the bytes behind it are the
+ * connection's first frames.  A status other than 101: WSG_UC_NOT_101, the
+ * headers are not walked.  Then the headers in order, names compared without
+ * case (ASCII): Connection must be "Upgrade" (no keep-alive form on this
+ * side); Upgrade must be "websocket"; Sec-WebSocket-Accept is decoded as
+ * WS::Base64Decode does (a byte outside the 64-letter alphabet, '=' and
+ * blanks among them, is skipped; six bits a letter, a byte whenever eight are
+ * held) into `got`, which is compared with expect = SHA-1(Base64(nonce) ||
+ * GUID) as strncmp(got, expect, min(|got|, 20)) does: in order, unequal bytes
+ * fail and equal NUL bytes pass at once.  So an empty value, a value that
+ * decodes to a prefix of the digest, one with more than 20 bytes behind a
+ * right digest and one that agrees up to a NUL byte of the digest all pass,
+ * as they do in the classes and the reference.  The first failing header ends
+ * the walk.  All three seen in front of the walk's end: accepted (a failing
+ * header behind them no longer counts); otherwise the failing header's code,
+ * or WSG_UC_MISSING when none failed.                                        */
+#define WSG_UC_INCOMPLETE      0   /* no header end yet, or the body is short: resubmit with more bytes */
+#define WSG_UC_ACCEPTED        1   /* handshaked */
+#define WSG_UC_BAD_HTTP        2   /* malformed status line or header line ("Invalid HTTP response") */
+#define WSG_UC_BAD_CONNECTION  3
+#define WSG_UC_BAD_UPGRADE     4
+#define WSG_UC_BAD_ACCEPT      5
+#define WSG_UC_MISSING         6   /* some of the three headers missing, none failing ("Invalid WebSocket response") */
+#define WSG_UC_NOT_101         7   /* a whole response with another status: no error text, not handshaked */
+#define WSG_UC_TOO_LONG        8   /* incomplete at max_response bytes or more: disconnect */
+
+typedef struct wsg_upgrade_reply {   /* 32 bytes */
+    uint64_t accept_off;   /* absolute wire offset of the trimmed value of the last Sec-WebSocket-Accept
+                              line the walk judged (a failing one is judged); 0 if none */
+    uint64_t body_off;     /* absolute offset of the body (hend); set with body_len for a whole, well-formed response */
+    uint32_t accept_len, body_len;   /* saturating at UINT32_MAX */
+    uint32_t _zero;        /* written as 0 */
+    uint16_t status;       /* the three digits, 0 while incomplete / malformed / too long */
+    uint8_t  code;         /* WSG_UC_* */
+    uint8_t  _pad;         /* written as 0 */
+} wsg_upgrade_reply;
+
+/* Stream j is d_wire[off, off + len) of d_span[j], one response per stream per
+ * call, judged against d_nonce[16j, 16j + 16): whatever follows `consumed` is
+ * not looked at.  d_span[j].consumed: 0 while the response is incomplete (or
+ * too long), hend for BAD_HTTP, hend + clen otherwise.  d_span[j].need: hend +
+ * clen, saturating, when only the body is missing, else 0.
+ * max_response: 0 for no limit; otherwise an incomplete response of len >=
+ * max_response gets WSG_UC_TOO_LONG.
+ * d_count[0..3): streams accepted, whole but not accepted (codes 2-7),
+ * WSG_UC_INCOMPLETE.
+ * A span past wire_len, or one that starts before the end of the span before
+ * it, is latched as wsg_frame_streams latches it (WSG_EINVAL under stream <<
+ * 8 | code); that stream gets WSG_UC_INCOMPLETE, consumed 0 and an otherwise
+ * zero record.  n_streams == 0 and empty streams are valid.  WSG_EINVAL for a
+ * NULL operand, d_wire or d_nonce not 16-byte aligned (d_wire readable to the
+ * end of its last 16-byte block), another operand not 8-byte aligned.
+ * Asynchronous on `stream`.  The call uses wsg_frame_streams' scratch of the
+ * ctx and is ordered across streams with those calls, under the same capture
+ * rule: run it once uncaptured with the same n_streams before capturing.     */
+int wsg_upgrade_client_streams(wsg_ctx* ctx, const uint8_t* d_wire, uint64_t wire_len,
+                               wsg_stream_span* d_span, uint32_t n_streams,
+                               const uint8_t* d_nonce /* 16 * n_streams */, uint64_t max_response,
+                               wsg_upgrade_reply* d_up, uint64_t* d_count /* 3 */, void* stream);
+
+/* The requests that go with those nonces.  d_tpl[0, tpl_len) is a request with
+ * a 24-byte hole at key_at (what onWSConnecting followed by SetBody()
+ * produces, the key's value aside); request j is d_req[j * tpl_len, (j + 1) *
+ * tpl_len): the template with Base64(d_nonce[16j, 16j + 16)) in the hole.  No
+ * byte of d_req at or behind n * tpl_len is written.
+ * WSG_EINVAL for key_at + 24 > tpl_len (so for tpl_len below 24), a NULL
+ * operand that n > 0 needs, d_req, d_tpl or d_nonce not 16-byte aligned
+ * (d_tpl readable to the end of its last 16-byte block); WSG_ENOMEM, decided
+ * on the host with nothing launched, when n * tpl_len > req_cap.
+ * Asynchronous on `stream`; no scratch.                                      */
+int wsg_upgrade_requests(wsg_ctx* ctx, const uint8_t* d_tpl, uint32_t tpl_len, uint32_t key_at,
+                         const uint8_t* d_nonce /* 16 * n */, uint32_t n, uint8_t* d_req, uint64_t req_cap,
+                         void* stream);
+
+/* One response judged on the host by the rule the kernels run (host memory, no
+ * ctx, no OpenSSL): buf[0, len) as one stream at offset 0 against nonce[16].
+ * *out as d_up[j], *consumed and *need (or NULL) as the span's.              */
+int wsg_upgrade_client_judge(const uint8_t* buf, uint64_t len, const uint8_t nonce[16], uint64_t max_response,
+                             wsg_upgrade_reply* out, uint64_t* consumed, uint64_t* need);
+
+/* One request on the host: out[0, tpl_len) = the template with Base64(nonce)
+ * at key_at.  WSG_EINVAL for key_at + 24 > tpl_len or a NULL operand.        */
+int wsg_upgrade_request(const uint8_t* tpl, uint32_t tpl_len, uint32_t key_at, const uint8_t nonce[16], uint8_t* out);
+
 /* ---- checked replies: an echo server that fails connections on the device -- */
 /* (Added without an ABI bump, as wsg_decode_messages was: symbols and
  * constants only.)

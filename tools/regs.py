@@ -3,7 +3,8 @@ out (which path sets the kernel's VGPR count), for the encode, lane, fan-out
 and XOR kernels, and for k_msg_gather
 (wsg_decode_messages; wsg_reply_messages runs it too), the reply plan, the
 framer, the UTF-8 check (dense and from the wire), the protocol check,
-the checked reply (wsg_reply_checked), the upgrade handshake (wsg_upgrade_streams), the carry
+the checked reply (wsg_reply_checked), the upgrade handshake (wsg_upgrade_streams), its client half
+(wsg_upgrade_client_streams, wsg_upgrade_requests), the carry
 (wsg_carry_streams) and the relay plan (wsg_relay_validated).  Compiles for gfx950 only (no GPU needed).
 
 usage: python tools/regs.py
@@ -75,6 +76,8 @@ if __name__ == "__main__":
                                              "k_proto_merge")),
                           ("wsg_upgrade.hip", ("k_upgrade_parse", "k_upgrade_scan_local", "k_upgrade_scan_blocks",
                                                "k_upgrade_accept", "k_upgrade_respond")),
+                          ("wsg_upgrade_client.hip", ("k_upclient_expect", "k_upclient_parse", "k_upclient_count_local",
+                                                      "k_upclient_count_blocks", "k_upgrade_requests")),
                           ("wsg_carry.hip", ("k_carry_sizes", "k_carry_scan_blocks", "k_carry_spans", "k_carry_copy")),
                           ("wsg_relay.hip", ("k_relay_local", "k_relay_frames<0>", "k_relay_frames<1>", "k_relay_blocks",
                                              "k_relay_streams_local", "k_relay_streams_blocks", "k_relay_finalize"))):
